@@ -9,6 +9,12 @@ Sessions are sharded across GPUs (data parallel — the production answer for
 an 8B backing model on an 8-GPU node); per-GPU work is fixed => weak scaling.
 
 Rank 0 prints one JSON line with the whole-job aggregate turns/sec.
+
+A plain run sets up, warms up, times the K steps and prints that line.
+`--dump-outputs DIR` additionally saves the tokens the last timed step
+returned (prompts, weights and sampling seed are fixed, so two builds can
+be compared output for output). `--full` is where any further measurement
+belongs; today the headline run is all there is.
 """
 from __future__ import annotations
 
@@ -41,7 +47,18 @@ def main() -> None:
                          "across ranks, tokens routed over all-to-all "
                          "(RCCL over xGMI); sessions stay rank-local")
     ap.add_argument("--device", default=None)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the tokens every "
+                         "session received in the last timed step to "
+                         "DIR/tokens.npy (float32, [sessions, decode_len]; "
+                         "tokens_rank<r>.npy per rank on multi-GPU runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements a plain run skips; the "
+                         "headline run is all this benchmark measures "
+                         "today, so the flag currently adds nothing")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     from kukeon_amd import parallel
     from kukeon_amd.engine.config import (EngineConfig, MODEL_PRESETS,
@@ -114,10 +131,36 @@ def main() -> None:
     sync()
     t0 = time.perf_counter()
     turns = 0
-    for _ in range(args.steps):
+    last_outs = []
+    for i in range(args.steps):
+        if args.dump_outputs and i == args.steps - 1:
+            # tap what engine.step() hands its caller during the last step
+            step = engine.step
+
+            def tapped_step():
+                outs = step()
+                last_outs.extend(outs)
+                return outs
+            engine.step = tapped_step
         turns += driver.run_round()
     sync()
     elapsed = time.perf_counter() - t0
+
+    if args.dump_outputs:
+        import numpy as np
+        # request ids are handed out in session order within a round
+        rids = sorted({o.req_id for o in last_outs})
+        row = {rid: i for i, rid in enumerate(rids)}
+        toks = np.full((len(rids), args.decode_len), -1.0, dtype=np.float32)
+        fill = [0] * len(rids)
+        for o in last_outs:
+            r = row[o.req_id]
+            n = len(o.new_tokens)
+            toks[r, fill[r]:fill[r] + n] = o.new_tokens
+            fill[r] += n
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        name = "tokens.npy" if world == 1 else f"tokens_rank{rank}.npy"
+        np.save(os.path.join(args.dump_outputs, name), toks)
 
     # max over ranks (slowest rank defines the job)
     if world > 1:

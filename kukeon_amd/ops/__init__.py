@@ -13,17 +13,32 @@ from . import reference
 
 _C = None
 _IMPORT_ERROR: Exception | None = None
-try:
-    from kukeon_amd import _C  # type: ignore
-except Exception as e:  # pragma: no cover - exercised only on broken installs
-    _IMPORT_ERROR = e
+
+
+def _load() -> None:
+    global _C, _IMPORT_ERROR
+    try:
+        from kukeon_amd import _C as ext  # type: ignore
+    except Exception as e:  # pragma: no cover - only on broken installs
+        _IMPORT_ERROR = e
+    else:
+        _C, _IMPORT_ERROR = ext, None
+
+
+_load()
 
 
 def native_available() -> bool:
+    # importing kukeon_amd.ops.build imports this package first, so in a
+    # fresh tree the extension only appears after this module was loaded
+    if _C is None:
+        _load()
     return _C is not None
 
 
 def _native():
+    if _C is None:
+        _load()
     if _C is None:
         raise RuntimeError(
             "kukeon_amd._C (gfx950 HIP extension) is not built but an op was "

@@ -218,14 +218,20 @@ def test_daemon_recreate_reprovisions_modelhub(tmp_path):
     rp = str(tmp_path / "run")
     assert runner.invoke(cli, ["--run-path", rp, "--local",
                                "init"]).exit_code == 0
-    r = runner.invoke(cli, ["--run-path", rp, "--local", "daemon",
-                            "recreate", "--gpus", "0"])
-    assert r.exit_code == 0, r.output
-    assert "modelhub cell recreated" in r.output
-    # idempotent: a second recreate deletes and re-provisions
-    r2 = runner.invoke(cli, ["--run-path", rp, "--local", "daemon",
-                             "recreate", "--gpus", "0"])
-    assert r2.exit_code == 0, r2.output
+    try:
+        r = runner.invoke(cli, ["--run-path", rp, "--local", "daemon",
+                                "recreate", "--gpus", "0"])
+        assert r.exit_code == 0, r.output
+        assert "modelhub cell recreated" in r.output
+        # idempotent: a second recreate deletes and re-provisions
+        r2 = runner.invoke(cli, ["--run-path", rp, "--local", "daemon",
+                                 "recreate", "--gpus", "0"])
+        assert r2.exit_code == 0, r2.output
+    finally:
+        # the provisioned modelhub is a real server process: take it down
+        # so the suite leaves nothing running
+        runner.invoke(cli, ["--run-path", rp, "--local", "uninstall",
+                            "--yes"])
 
 
 def test_version_and_autocomplete_smoke():

@@ -778,6 +778,10 @@ def test_secret_file_channel_binds(ctl):
     (reference ctr secret file injection)."""
     import os as _os
 
+    # the bind list is only built for a private mount namespace; the probe
+    # for that depends on the privileges of whoever runs the suite, and
+    # the FakeRuntime mounts nothing, so pin the capability here
+    ctl.ns_caps["mnt"] = True
     ctl.put_secret(api.SecretDoc(
         metadata=api.Metadata(name="tok"),
         spec=api.SecretSpec(realm_id="default", space_id="default",

@@ -5,7 +5,9 @@ a short /tmp socket with --reconcile-interval 0 so tests don't race the
 loop."""
 import json
 import os
+import shutil
 import socket
+import tempfile
 import time
 import uuid
 from pathlib import Path
@@ -22,9 +24,13 @@ from kukeon_amd.tty import attach as attach_mod
 
 
 @pytest.fixture
-def harness(tmp_path):
+def harness():
     sock = f"/tmp/kuke-{uuid.uuid4().hex[:10]}.sock"
-    ctl = Controller(str(tmp_path / "run"), gpu_devices=[])
+    # attach sockets live under the run path and AF_UNIX paths are capped
+    # at 107 bytes, so the run path is kept as short as the daemon socket
+    # rather than under pytest's (arbitrarily deep) tmp_path
+    run_root = tempfile.mkdtemp(prefix="kuke-", dir="/tmp")
+    ctl = Controller(os.path.join(run_root, "run"), gpu_devices=[])
     ctl.bootstrap()
     srv = Server(ctl, sock, reconcile_interval=0)
     srv.start()
@@ -43,6 +49,7 @@ def harness(tmp_path):
                         pass
     client.close()
     srv.stop()
+    shutil.rmtree(run_root, ignore_errors=True)
 
 
 CELL_YAML = """
@@ -88,7 +95,7 @@ def test_apply_start_stop_cell(harness):
                        name="busy")
 
 
-def test_interactive_pty_attach(harness):
+def test_interactive_pty_attach(pty_device, harness):
     ctl, srv, client = harness
     doc = api.CellDoc(
         metadata=api.Metadata(name="shelly"),
@@ -355,7 +362,7 @@ def test_container_repo_setup(harness, tmp_path):
                     name="repocell")
 
 
-def test_scm_rights_fd_attach(harness):
+def test_scm_rights_fd_attach(pty_device, harness):
     """SCM_RIGHTS fast path (reference cmd/kuketty/main.go:17-30): the
     first attacher gets the PTY master fd and pumps bytes with no shim
     relay; a concurrent second attacher falls back to the relay path;

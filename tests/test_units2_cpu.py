@@ -293,7 +293,7 @@ def test_delete_image_refuses_while_referenced(tmp_path):
     ctl.delete_image("tool:v2")               # unreferenced: fine
 
 
-def test_capture_log_rotation(tmp_path):
+def test_capture_log_rotation(pty_device, tmp_path):
     """The shim's capture file rotates at its size cap instead of
     growing unbounded (one .1 generation kept for kuke log)."""
     import json
