@@ -1,4 +1,9 @@
-"""Mixtral-8x7B decoder: Llama attention + MoE MLP with two routes.
+"""Mixtral-8x7B decoder: Llama attention + MoE MLP with three routes.
+
+Grouped (T > 128 under hipGraph capture, or eager up to _GROUPED_MAX_T):
+routing and the expert sort in one device pass, both expert projections as
+one grouped GEMM each with per-expert row ranges read from device memory —
+static shapes, no host sync, no redundant flops.
 
 Prefill (large T): softmax top-k routing, token permute into expert-sorted
 order via the gfx950 HIP permute kernels, per-expert fused gate_up/down
@@ -18,6 +23,8 @@ all-reduce is per-link bound.
 """
 from __future__ import annotations
 
+import os
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -25,6 +32,14 @@ import torch.nn.functional as F
 from kukeon_amd import ops, parallel
 from kukeon_amd.engine.config import ModelConfig
 from kukeon_amd.models.llama import (AttnMeta, LlamaAttention, _init_weight)
+
+# Largest eager T that takes the grouped-GEMM route (device-side routing +
+# one GEMM launch for all experts). From the measured sweep in docs/perf.md:
+# above it the per-expert hipBLASLt loop of the sparse route wins. Under
+# hipGraph capture the grouped route runs at every T > 128 regardless — the
+# sparse route's host sync cannot be captured. 0 turns the route off in
+# eager mode.
+_GROUPED_MAX_T = int(os.environ.get("KUKEON_MOE_GROUPED_MAX_T", "192"))
 
 
 class MixtralMoE(nn.Module):
@@ -65,7 +80,17 @@ class MixtralMoE(nn.Module):
             return self._forward_ep(x)
         if x.is_cuda and T <= 128:
             return self._forward_dense(x)
+        if (x.is_cuda and self._grouped_eligible(x)
+                and (T <= _GROUPED_MAX_T
+                     or torch.cuda.is_current_stream_capturing())):
+            return self._forward_grouped(x)
         return self._forward_sparse(x)
+
+    def _grouped_eligible(self, x: torch.Tensor) -> bool:
+        # the shapes moe_route_sort / moe_grouped_gemm accept
+        return (x.dtype == torch.bfloat16 and x.shape[1] % 64 == 0
+                and self.inter % 64 == 0 and self.E <= 32
+                and self.K <= min(4, self.E))
 
     def _expert_mlp(self, xs: torch.Tensor, e: int) -> torch.Tensor:
         gu = F.linear(xs, self.gate_up_w[e])
@@ -195,6 +220,40 @@ class MixtralMoE(nn.Module):
         ops.moe_scatter_tokens(out, out_expanded,
                                inv.reshape(T, self.K).to(torch.int32),
                                topv.float().contiguous(), self.K)
+        return parallel.tp_all_reduce(out)
+
+    def _grouped_mlp(self, a: torch.Tensor, a_rows, offsets: torch.Tensor,
+                     rows: int) -> torch.Tensor:
+        """gate_up -> SwiGLU -> down for `rows` expert-sorted slots, one
+        grouped-GEMM launch per projection. Slot r reads a[a_rows[r]]
+        (a[r] when a_rows is None); expert e owns the slots
+        [offsets[e], offsets[e+1]), read on the device."""
+        gu = torch.empty(rows, 2 * self.inter, dtype=a.dtype, device=a.device)
+        ops.moe_grouped_gemm(gu, a, a_rows, self.gate_up_w, offsets)
+        act = torch.empty(rows, self.inter, dtype=a.dtype, device=a.device)
+        ops.silu_mul(act, gu)
+        y = torch.empty(rows, self.down_w.shape[1], dtype=a.dtype,
+                        device=a.device)
+        ops.moe_grouped_gemm(y, act, None, self.down_w, offsets)
+        return y
+
+    def _forward_grouped(self, x: torch.Tensor) -> torch.Tensor:
+        """Static-shape sparse route: routing and the expert sort stay on
+        the device and both projections run as one grouped GEMM over all
+        experts, so there is no host sync, every allocation is fixed by T,
+        and the layer is hipGraph-capturable at any T — without the dense
+        route's E/K-fold redundant flops."""
+        T = x.shape[0]
+        logits = F.linear(x, self.router_w)                   # [T, E] bf16
+        topk_w = torch.empty(T, self.K, dtype=torch.float32, device=x.device)
+        row_map = torch.empty(T * self.K, dtype=torch.int32, device=x.device)
+        inv_map = torch.empty(T, self.K, dtype=torch.int32, device=x.device)
+        offsets = torch.empty(self.E + 1, dtype=torch.int32, device=x.device)
+        ops.moe_route_sort(topk_w, row_map, inv_map, offsets, logits, self.K)
+        # the gather happens in the gate_up A-tile load: no [T*K,H] copy
+        y = self._grouped_mlp(x, row_map, offsets, T * self.K)
+        out = torch.empty_like(x)
+        ops.moe_scatter_tokens(out, y, inv_map, topk_w, self.K)
         return parallel.tp_all_reduce(out)
 
 

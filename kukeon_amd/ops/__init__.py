@@ -295,3 +295,20 @@ def moe_gather_tokens(out, input, row_map) -> None:
 
 def moe_scatter_tokens(out, input, inv_map, weights, top_k: int) -> None:
     _impl(input).moe_scatter_tokens(out, input, inv_map, weights, top_k)
+
+
+def moe_route_sort(topk_w, row_map, inv_map, offsets, logits, k: int) -> None:
+    """Top-k routing on the raw logits (ties to the lowest expert id) and
+    the stable sort of the (token, j) pairs by expert, all on the device:
+    no host read, so the MoE layer's launch shapes never depend on the
+    routing."""
+    _impl(logits).moe_route_sort(topk_w, row_map, inv_map, offsets, logits,
+                                 k)
+
+
+def moe_grouped_gemm(out, a, a_rows, w, offsets) -> None:
+    """out[r] = a[a_rows[r]] @ w[e].T for r in [offsets[e], offsets[e+1]),
+    every expert in one launch. `a_rows` None/empty means identity."""
+    if a_rows is None:
+        a_rows = torch.empty(0, dtype=torch.int32, device=a.device)
+    _impl(a).moe_grouped_gemm(out, a, a_rows, w, offsets)

@@ -67,6 +67,12 @@ void moe_gather_tokens(torch::Tensor out, torch::Tensor input,
 void moe_scatter_tokens(torch::Tensor out, torch::Tensor input,
                         torch::Tensor row_map, torch::Tensor weights,
                         int64_t top_k);
+void moe_route_sort(torch::Tensor topk_w, torch::Tensor row_map,
+                    torch::Tensor inv_map, torch::Tensor offsets,
+                    torch::Tensor logits, long K);
+void moe_grouped_gemm(torch::Tensor out, torch::Tensor a,
+                      torch::Tensor a_rows, torch::Tensor w,
+                      torch::Tensor offsets);
 }  // namespace kukeon
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -117,4 +123,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "out = sum_e w[t,e]*y[e,t,:], zero-weight experts skipped");
   m.def("moe_scatter_tokens", &kukeon::moe_scatter_tokens,
         "MoE unpermute + weighted combine");
+  m.def("moe_route_sort", &kukeon::moe_route_sort,
+        "top-k routing + stable expert sort on the device, one launch");
+  m.def("moe_grouped_gemm", &kukeon::moe_grouped_gemm,
+        "out[r] = a[a_rows[r]] @ w[e].T, expert row ranges from device");
 }

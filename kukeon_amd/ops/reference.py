@@ -248,3 +248,35 @@ def moe_dense_combine(out: torch.Tensor, y: torch.Tensor,
                       wdense: torch.Tensor) -> None:
     acc = (y.float() * wdense.t().unsqueeze(-1)).sum(dim=0)
     out.copy_(acc.to(out.dtype))
+
+
+def moe_route_sort(topk_w: torch.Tensor, row_map: torch.Tensor,
+                   inv_map: torch.Tensor, offsets: torch.Tensor,
+                   logits: torch.Tensor, K: int) -> None:
+    T, E = logits.shape
+    # a stable descending sort keeps equal logits in expert-id order: the
+    # kernel's "ties go to the lowest expert id" rule
+    vals, idx = torch.sort(logits.float(), dim=-1, descending=True,
+                           stable=True)
+    topv, topi = vals[:, :K], idx[:, :K]
+    topk_w.copy_(torch.softmax(topv, dim=-1).reshape(topk_w.shape))
+    flat = topi.reshape(-1)
+    order = torch.argsort(flat, stable=True)        # slots by (expert, t*K+j)
+    inv = torch.empty_like(order)
+    inv[order] = torch.arange(order.numel(), device=order.device)
+    row_map.copy_((order // K).to(torch.int32).reshape(row_map.shape))
+    inv_map.copy_(inv.to(torch.int32).reshape(inv_map.shape))
+    counts = torch.bincount(flat, minlength=E)
+    offsets[0] = 0
+    offsets[1:] = torch.cumsum(counts, 0).to(torch.int32)
+
+
+def moe_grouped_gemm(out: torch.Tensor, a: torch.Tensor,
+                     a_rows: torch.Tensor, w: torch.Tensor,
+                     offsets: torch.Tensor) -> None:
+    src = a if a_rows is None or a_rows.numel() == 0 else a[a_rows.long()]
+    offs = offsets.tolist()
+    for e in range(w.shape[0]):
+        lo, hi = offs[e], offs[e + 1]
+        if hi > lo:
+            out[lo:hi] = (src[lo:hi].float() @ w[e].float().T).to(out.dtype)
