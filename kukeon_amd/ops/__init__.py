@@ -135,54 +135,68 @@ def _skinny5_wins(rows: int, N: int, K: int) -> bool:
     return (N, K) in ((4096, 14336), (8192, 28672))
 
 
+def _skinny_kind(x: torch.Tensor, w: torch.Tensor, fused: bool):
+    """Which skinny kernel runs x @ w.T: "v5", "v1", or None for the
+    library. `fused` asks for the reduce + residual-add + RMSNorm epilogue,
+    which exists only at TP=1 and holds a whole row per block."""
+    rows = x.shape[0]
+    if not (x.is_cuda and x.dim() == 2 and rows <= 64
+            and x.dtype == torch.bfloat16):
+        return None
+    N, K = w.shape
+    if fused:
+        from kukeon_amd import parallel
+        if not (parallel.tp_size() == 1 and N % 2048 == 0 and N <= 8192):
+            return None
+    if (N % 128 == 0 and K % 128 == 0
+            and (_USE_SKINNY == "5" or _skinny5_wins(rows, N, K))):
+        return "v5"
+    if (N % 64 == 0 and K % 32 == 0
+            and (_USE_SKINNY == "1" or _skinny_wins(rows, N, K))):
+        return "v1"
+    return None
+
+
+# split-K factor per (kind, N, K), asked of the launchers' own plan once
+# (so their env overrides are read at a shape's first use, like the
+# switches above at import)
+_SKINNY_SPLITK = {}
+
+
+def _skinny_workspace(device: torch.device, kind: str, N: int,
+                      K: int) -> torch.Tensor:
+    """The device's split-K slab buffer, grown to the 64 * N * splitk
+    floats the `kind` launcher (a skinny_splitk kind) may write."""
+    splitk = _SKINNY_SPLITK.get((kind, N, K))
+    if splitk is None:
+        splitk = _SKINNY_SPLITK[kind, N, K] = _native().skinny_splitk(
+            kind, N, K)
+    need = 64 * N * splitk
+    key = (device.index or 0)
+    ws = _SKINNY_WS.get(key)
+    if ws is None or ws.numel() < need:
+        # grown only outside graph capture (engine warmup runs eager)
+        if ws is not None:
+            _SKINNY_WS_RETIRED.append(ws)
+        ws = torch.empty(need, dtype=torch.float32, device=device)
+        _SKINNY_WS[key] = ws
+    return ws
+
+
 def linear(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
     """F.linear with the weight-streaming skinny-GEMM kernel on the decode
     shapes where it measured faster than hipBLASLt; hipBLASLt otherwise."""
-    rows = x.shape[0]
-    if (x.is_cuda and x.dim() == 2 and rows <= 64
-            and w.shape[0] % 128 == 0 and w.shape[1] % 128 == 0
-            and x.dtype == torch.bfloat16
-            and (_USE_SKINNY == "5"
-                 or _skinny5_wins(rows, w.shape[0], w.shape[1]))):
-        N = w.shape[0]
-        K = w.shape[1]
-        out = torch.empty(rows, N, dtype=x.dtype, device=x.device)
-        key = (x.device.index or 0)
-        ws = _SKINNY_WS.get(key)
-        ngroups = N // 128
-        nslices = -(-K // 128)
-        splitk = 1 if ngroups >= 256 else min(nslices, -(-256 // ngroups))
-        need = max(1, splitk) * 64 * N
-        if ws is None or ws.numel() < need:
-            if ws is not None:
-                _SKINNY_WS_RETIRED.append(ws)
-            ws = torch.empty(need, dtype=torch.float32, device=x.device)
-            _SKINNY_WS[key] = ws
+    kind = _skinny_kind(x, w, fused=False)
+    if kind is None:
+        return torch.nn.functional.linear(x, w)
+    N, K = w.shape
+    out = torch.empty(x.shape[0], N, dtype=x.dtype, device=x.device)
+    ws = _skinny_workspace(x.device, kind, N, K)
+    if kind == "v5":
         _native().skinny_gemm5(out, x, w, ws)
-        return out
-    if (x.is_cuda and x.dim() == 2 and rows <= 64
-            and w.shape[0] % 64 == 0 and w.shape[1] % 32 == 0
-            and x.dtype == torch.bfloat16
-            and (_USE_SKINNY == "1"
-                 or _skinny_wins(rows, w.shape[0], w.shape[1]))):
-        N = w.shape[0]
-        K = w.shape[1]
-        out = torch.empty(rows, N, dtype=x.dtype, device=x.device)
-        key = (x.device.index or 0)
-        ws = _SKINNY_WS.get(key)
-        ntiles = N // 64
-        nslices = -(-K // 256)
-        splitk = 1 if ntiles >= 512 else min(nslices, -(-256 // ntiles))
-        need = max(1, splitk) * 64 * N
-        if ws is None or ws.numel() < need:
-            # grown only outside graph capture (engine warmup runs eager)
-            if ws is not None:
-                _SKINNY_WS_RETIRED.append(ws)
-            ws = torch.empty(need, dtype=torch.float32, device=x.device)
-            _SKINNY_WS[key] = ws
+    else:
         _native().skinny_gemm(out, x, w, ws)
-        return out
-    return torch.nn.functional.linear(x, w)
+    return out
 
 
 def linear_add_rmsnorm(x: torch.Tensor, w: torch.Tensor,
@@ -195,51 +209,23 @@ def linear_add_rmsnorm(x: torch.Tensor, w: torch.Tensor,
     <1us of work. Mutates `residual` (+= x@w.T) and returns the normed
     activations, exactly like linear() followed by fused_add_rmsnorm().
     """
-    from kukeon_amd import parallel
-    rows = x.shape[0]
+    kind = _skinny_kind(x, w, fused=True)
+    if kind is None:
+        from kukeon_amd import parallel
+        h = parallel.tp_all_reduce(linear(x, w))
+        fused_add_rmsnorm(h, residual, norm_weight, eps)
+        return h
     N, K = w.shape
-    if (x.is_cuda and parallel.tp_size() == 1 and x.dim() == 2
-            and rows <= 64 and N % 2048 == 0 and N <= 8192 and K % 128 == 0
-            and x.dtype == torch.bfloat16
-            and (_USE_SKINNY == "5" or _skinny5_wins(rows, N, K))):
-        key = (x.device.index or 0)
-        ws = _SKINNY_WS.get(key)
-        ngroups = N // 128
-        nslices = -(-K // 128)
-        splitk = min(nslices, -(-256 // ngroups))
-        need = max(1, splitk) * 64 * N
-        if ws is None or ws.numel() < need:
-            if ws is not None:
-                _SKINNY_WS_RETIRED.append(ws)
-            ws = torch.empty(need, dtype=torch.float32, device=x.device)
-            _SKINNY_WS[key] = ws
-        normed = torch.empty(rows, N, dtype=x.dtype, device=x.device)
+    normed = torch.empty(x.shape[0], N, dtype=x.dtype, device=x.device)
+    if kind == "v5":
+        ws = _skinny_workspace(x.device, "v5_fused", N, K)
         _native().skinny_gemm5_fused_norm(normed, x, w, ws, residual,
                                           norm_weight, eps)
-        return normed
-    if (x.is_cuda and parallel.tp_size() == 1 and x.dim() == 2
-            and rows <= 64 and N % 2048 == 0 and N <= 8192 and K % 32 == 0
-            and x.dtype == torch.bfloat16
-            and (_USE_SKINNY == "1" or _skinny_wins(rows, N, K))):
-        key = (x.device.index or 0)
-        ws = _SKINNY_WS.get(key)
-        ntiles = N // 64
-        nslices = -(-K // 256)
-        splitk = min(nslices, -(-256 // ntiles))
-        need = max(1, splitk) * 64 * N
-        if ws is None or ws.numel() < need:
-            if ws is not None:
-                _SKINNY_WS_RETIRED.append(ws)
-            ws = torch.empty(need, dtype=torch.float32, device=x.device)
-            _SKINNY_WS[key] = ws
-        normed = torch.empty(rows, N, dtype=x.dtype, device=x.device)
+    else:
+        ws = _skinny_workspace(x.device, "v1", N, K)
         _native().skinny_gemm_fused_norm(normed, x, w, ws, residual,
                                          norm_weight, eps)
-        return normed
-    h = parallel.tp_all_reduce(linear(x, w))
-    fused_add_rmsnorm(h, residual, norm_weight, eps)
-    return h
-
+    return normed
 
 
 def mlp_down_fused(gu: torch.Tensor, w: torch.Tensor,
@@ -252,26 +238,11 @@ def mlp_down_fused(gu: torch.Tensor, w: torch.Tensor,
     disappear; profiles/r02_progress.md). `gu` is the fused gate_up GEMM
     output [rows, 2K]. Equivalent to silu_mul + linear_add_rmsnorm.
     """
-    from kukeon_amd import parallel
     rows = gu.shape[0]
     N, K = w.shape
-    if (_FUSE_SILU and gu.is_cuda and parallel.tp_size() == 1
-            and gu.dim() == 2
-            and rows <= 64 and gu.shape[1] == 2 * K
-            and N % 2048 == 0 and N <= 8192 and K % 128 == 0
-            and gu.dtype == torch.bfloat16
-            and (_USE_SKINNY == "5" or _skinny5_wins(rows, N, K))):
-        key = (gu.device.index or 0)
-        ws = _SKINNY_WS.get(key)
-        ngroups = N // 128
-        nslices = -(-K // 128)
-        splitk = min(nslices, -(-256 // ngroups))
-        need = max(1, splitk) * 64 * N
-        if ws is None or ws.numel() < need:
-            if ws is not None:
-                _SKINNY_WS_RETIRED.append(ws)
-            ws = torch.empty(need, dtype=torch.float32, device=gu.device)
-            _SKINNY_WS[key] = ws
+    if (_FUSE_SILU and gu.dim() == 2 and gu.shape[1] == 2 * K
+            and _skinny_kind(gu, w, fused=True) == "v5"):
+        ws = _skinny_workspace(gu.device, "v5_fused", N, K)
         normed = torch.empty(rows, N, dtype=gu.dtype, device=gu.device)
         _native().skinny_gemm5_silu_fused_norm(normed, gu, w, ws,
                                                residual, norm_weight, eps)

@@ -30,16 +30,10 @@ void mfma_probe16(torch::Tensor out, torch::Tensor a, torch::Tensor b);
 void mfma_probe16k(torch::Tensor out, torch::Tensor a, torch::Tensor b);
 void skinny_gemm2(torch::Tensor out, torch::Tensor x, torch::Tensor w,
                   torch::Tensor ws);
-void skinny_gemm4(torch::Tensor out, torch::Tensor x, torch::Tensor w,
-                  torch::Tensor ws);
 void skinny_gemm5(torch::Tensor out, torch::Tensor x, torch::Tensor w,
                   torch::Tensor ws);
 void skinny_gemm6(torch::Tensor out, torch::Tensor x, torch::Tensor w,
                   torch::Tensor ws);
-void skinny_gemm6_fused_norm(torch::Tensor normed, torch::Tensor x,
-                             torch::Tensor w, torch::Tensor ws,
-                             torch::Tensor residual, torch::Tensor nw,
-                             double eps);
 void skinny_gemm5_silu_fused_norm(torch::Tensor normed, torch::Tensor gu,
                                   torch::Tensor w, torch::Tensor ws,
                                   torch::Tensor residual, torch::Tensor nw,
@@ -47,6 +41,7 @@ void skinny_gemm5_silu_fused_norm(torch::Tensor normed, torch::Tensor gu,
 void skinny_gemm(torch::Tensor out, torch::Tensor x, torch::Tensor w,
                  torch::Tensor ws);
 void glds_probe(torch::Tensor out, torch::Tensor src);
+int64_t skinny_splitk(const std::string& kind, int64_t N, int64_t K);
 void skinny_gemm5_fused_norm(torch::Tensor normed, torch::Tensor x,
                              torch::Tensor w, torch::Tensor ws,
                              torch::Tensor residual, torch::Tensor nw,
@@ -94,19 +89,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "16x16x16 (K=16) bf16 MFMA fragment-layout probe");
   m.def("skinny_gemm6", &kukeon::skinny_gemm6,
         "decode GEMM v6 (barrier-free register-x pipeline)");
-  m.def("skinny_gemm6_fused_norm", &kukeon::skinny_gemm6_fused_norm,
-        "v6 + fused split-K reduce + residual add + RMSNorm");
   m.def("skinny_gemm5_silu_fused_norm",
         &kukeon::skinny_gemm5_silu_fused_norm,
         "silu(gate)*up + down GEMM + reduce + add + RMSNorm fused");
   m.def("skinny_gemm5", &kukeon::skinny_gemm5,
         "full-line W stream via wave-private LDS image (v5)");
-  m.def("skinny_gemm4", &kukeon::skinny_gemm4,
-        "G=4 deep-pipeline weight-streaming GEMM");
   m.def("skinny_gemm2", &kukeon::skinny_gemm2,
         "G-walk hand-counted weight-streaming GEMM (v2)");
   m.def("skinny_gemm", &kukeon::skinny_gemm,
         "weight-streaming decode GEMM (M<=64)");
+  m.def("skinny_splitk", &kukeon::skinny_splitk,
+        "split-K factor the skinny launcher of `kind` (v1, v2, v5, v5_fused, "
+        "v6) uses for [N, K]; host-only",
+        py::arg("kind"), py::arg("N"), py::arg("K"));
   m.def("glds_probe", &kukeon::glds_probe,
         "asm global_lds round-trip validator");
   m.def("skinny_gemm5_fused_norm", &kukeon::skinny_gemm5_fused_norm,

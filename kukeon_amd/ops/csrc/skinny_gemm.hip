@@ -16,10 +16,21 @@
 //     o-projection path.
 // Grid: (N/64, splitk); block = 4 waves, wave w owns N rows [64b+16w, +16)
 // of every slice the block walks. Dispatched per shape where it beats
-// hipBLASLt cold-LLC (ops/__init__.py _skinny_wins).
+// hipBLASLt cold-LLC (ops/__init__.py _skinny_kind).
+//
+// Layout of this file: the kernels first — v1 (above; o-projection), the
+// two split-K epilogues, v2 (G-tile walk, hand-counted waits), v5
+// (full-line W stream; down-projection) and v6 (barrier-free); v2, v6
+// and v5's silu path are tested negative results. The host side sits at
+// the end: one split-K plan (skinny_plan, exported to Python as
+// skinny_splitk so the workspace is sized by the same formula), one
+// launcher skeleton (run_reduce / run_reduce_add_rmsnorm), and one short
+// entry point per variant.
 #include "common.h"
 #include <torch/extension.h>
 #include <c10/hip/HIPStream.h>
+#include <string>
+#include <type_traits>
 
 namespace kukeon {
 
@@ -46,15 +57,6 @@ constexpr int U = 8;  // W k-chunks (of 32) per batch; 1 batch per slice
 // parked on memory 74% of their cycles with nothing to hide behind.
 // 256-wide slices halve the LDS (2 workgroups/CU, 2 waves/SIMD) at the
 // cost of twice the slice turnarounds.
-
-__global__ void skinny_zero_kernel(float* __restrict__ ws, long n) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i * 4 + 3 < n) {
-    *reinterpret_cast<float4*>(ws + i * 4) = float4{0.f, 0.f, 0.f, 0.f};
-  } else {
-    for (long j = i * 4; j < min(n, i * 4 + 4); ++j) ws[j] = 0.f;
-  }
-}
 
 DEV_INLINE int xswz(int row, int byte_in_row) {
   return row * (KSLICE * 2) + (byte_in_row ^ ((row & 15) << 4));
@@ -289,6 +291,81 @@ __global__ __launch_bounds__(256) void skinny_gemm_kernel(
   }
 }
 
+// reduce the split-K slabs and cast to bf16
+__global__ void skinny_reduce_kernel(unsigned short* __restrict__ out,
+                                     const float* __restrict__ ws, long n,
+                                     int splitk) {
+  const long i = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 8;
+  if (i + 7 < n) {
+    float v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (int s = 0; s < splitk; ++s) {
+      const float4 a = *reinterpret_cast<const float4*>(ws + s * n + i);
+      const float4 b = *reinterpret_cast<const float4*>(ws + s * n + i + 4);
+      v[0] += a.x; v[1] += a.y; v[2] += a.z; v[3] += a.w;
+      v[4] += b.x; v[5] += b.y; v[6] += b.z; v[7] += b.w;
+    }
+    *reinterpret_cast<uint4*>(out + i) = pack_bf16x8(v);
+  } else {
+    for (long j = i; j < n; ++j) {
+      float acc = 0.f;
+      for (int s = 0; s < splitk; ++s) acc += ws[s * n + j];
+      out[j] = f2us(acc);
+    }
+  }
+}
+
+// Split-K reduce fused with residual-add + RMSNorm: the decode o-proj's
+// epilogue pair (skinny_reduce 5.0us + fused_add_rmsnorm 5.4us) was two
+// launches at the ~4.5us in-graph dispatch floor each for <1us of real
+// work. One block per row: sum the slabs, update the residual in place,
+// one block-reduce for the mean square, write the normed activations.
+__global__ __launch_bounds__(256) void skinny_reduce_add_rmsnorm_kernel(
+    unsigned short* __restrict__ normed,    // [M, N] bf16
+    unsigned short* __restrict__ residual,  // [M, N] bf16, updated
+    const float* __restrict__ ws,           // [splitk, M, N] f32
+    const unsigned short* __restrict__ nw,  // [N]
+    int N, long total, int splitk, float eps) {
+  const int t = blockIdx.x;
+  __shared__ float red[16];
+  float vals[32];  // up to N = 8192 at 256 threads x 8 elems
+  const int nchunk = N / (256 * 8);
+  float sq = 0.f;
+  for (int c = 0; c < nchunk; ++c) {
+    const int n0 = (c * 256 + threadIdx.x) * 8;
+    const long off = (long)t * N + n0;
+    const bf16x8 r = load_bf16x8(residual + off);
+    float acc[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[j] = r.f(j);
+    for (int s = 0; s < splitk; ++s) {
+      const float4 a =
+          *reinterpret_cast<const float4*>(ws + (long)s * total + off);
+      const float4 b =
+          *reinterpret_cast<const float4*>(ws + (long)s * total + off + 4);
+      acc[0] += a.x; acc[1] += a.y; acc[2] += a.z; acc[3] += a.w;
+      acc[4] += b.x; acc[5] += b.y; acc[6] += b.z; acc[7] += b.w;
+    }
+    *reinterpret_cast<uint4*>(residual + off) = pack_bf16x8(acc);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      // norm of the bf16-rounded residual, matching the two-kernel path
+      const float v = us2f(f2us(acc[j]));
+      vals[c * 8 + j] = v;
+      sq += v * v;
+    }
+  }
+  sq = block_reduce(sq, red, SumOp{}, 0.f);
+  const float rs = __frsqrt_rn(sq / N + eps);
+  for (int c = 0; c < nchunk; ++c) {
+    const int n0 = (c * 256 + threadIdx.x) * 8;
+    const bf16x8 wv = load_bf16x8(nw + n0);
+    float o[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) o[j] = vals[c * 8 + j] * rs * wv.f(j);
+    *reinterpret_cast<uint4*>(normed + (long)t * N + n0) = pack_bf16x8(o);
+  }
+}
+
 // ===========================================================================
 // skinny GEMM v2 — G-tile walk with hand-counted W stream (round 2).
 //
@@ -310,15 +387,6 @@ __global__ __launch_bounds__(256) void skinny_gemm_kernel(
 //     stream never goes dry at a slice boundary.
 // Requires K%256==0, N%128==0 (all decode shapes qualify).
 // ===========================================================================
-
-__global__ void skinny_reduce_kernel(unsigned short* __restrict__ out,
-                                     const float* __restrict__ ws, long n,
-                                     int splitk);
-__global__ __launch_bounds__(256) void skinny_reduce_add_rmsnorm_kernel(
-    unsigned short* __restrict__ normed,
-    unsigned short* __restrict__ residual, const float* __restrict__ ws,
-    const unsigned short* __restrict__ nw, int N, long total, int splitk,
-    float eps);
 
 DEV_INLINE void issue_w8(u32x4_t (&reg)[8], const unsigned short* p) {
   // 8 nt 16B loads at 64 B stride (one 256-k slice of one W row per lane
@@ -353,7 +421,7 @@ DEV_INLINE void consume8(u32x4_t (&wreg)[8], const unsigned short* xb,
   }
 }
 
-template <int MT, bool SPLIT, int SMASK = 0>
+template <int MT, bool SPLIT>
 __global__ __launch_bounds__(256) void skinny2_kernel(
     unsigned short* __restrict__ out,      // [M, N] bf16 (SPLIT=false)
     float* __restrict__ ws,                // [splitk, M, N] f32 (SPLIT)
@@ -438,94 +506,6 @@ __global__ __launch_bounds__(256) void skinny2_kernel(
       } else {
         out[off0] = f2us(acc0[m][r]);
         out[off1] = f2us(acc1[m][r]);
-      }
-    }
-  }
-}
-
-// G=4 variant: four N-tiles per block, four static W register sets, 32
-// loads in flight per wave (128 KB per CU) — sized so the laden memory
-// latency under full load (~3 us) still sustains the per-CU share of HBM
-// bandwidth by Little's law. Same never-drain discipline as skinny2 v3.
-template <int MT, bool SPLIT>
-__global__ __launch_bounds__(256) void skinny4_kernel(
-    unsigned short* __restrict__ out, float* __restrict__ ws,
-    const unsigned short* __restrict__ x,
-    const unsigned short* __restrict__ w, int M, int N, long K) {
-  __shared__ __align__(16) unsigned short xbuf[2][64 * KSLICE];
-  const int wid = threadIdx.x / WAVE;
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int row16 = lane & 15;
-  const int kgrp = lane >> 4;
-  f32x4_t acc0[MT], acc1[MT], acc2[MT], acc3[MT];
-#pragma unroll
-  for (int m = 0; m < MT; ++m) {
-    acc0[m] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-    acc1[m] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-    acc2[m] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-    acc3[m] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-  }
-  const long kadv = (long)gridDim.y * KSLICE;
-  const long ks0 = (long)blockIdx.y * KSLICE;
-  if (ks0 >= K) return;
-  u32x4_t w0[8], w1[8], w2[8], w3[8];
-  const int nb = blockIdx.x * 4;
-  const unsigned short* p0 =
-      w + (long)((nb + 0) * 64 + wid * 16 + row16) * K + ks0 + 8 * kgrp;
-  const unsigned short* p1 =
-      w + (long)((nb + 1) * 64 + wid * 16 + row16) * K + ks0 + 8 * kgrp;
-  const unsigned short* p2 =
-      w + (long)((nb + 2) * 64 + wid * 16 + row16) * K + ks0 + 8 * kgrp;
-  const unsigned short* p3 =
-      w + (long)((nb + 3) * 64 + wid * 16 + row16) * K + ks0 + 8 * kgrp;
-
-  glds_stage_x(xbuf[0], x, K, ks0, KSLICE, M, wid, lane);
-  issue_w8(w0, p0);
-  issue_w8(w1, p1);
-  issue_w8(w2, p2);
-  issue_w8(w3, p3);
-  int cur = 0;
-  for (long ks = ks0; ks < K; ks += kadv, cur ^= 1) {
-    // entry: glds(s) oldest, t0..t3 (32 loads) younger
-    asm volatile("s_waitcnt vmcnt(32)" ::: "memory");
-    __syncthreads();
-    const unsigned short* xb = xbuf[cur];
-    const long ksn = ks + kadv;
-    consume8<MT, 24>(w0, xb, acc0, row16, kgrp);   // vmcnt(31-u)
-    glds_stage_x(xbuf[cur ^ 1], x, K, (ksn < K ? ksn : 0), KSLICE, M,
-                 wid, lane);
-    const unsigned short* p0n = (ksn < K) ? p0 + kadv : p0;
-    issue_w8(w0, p0n);
-    consume8<MT, 32>(w1, xb, acc1, row16, kgrp);   // vmcnt(39-u)
-    const unsigned short* p1n = (ksn < K) ? p1 + kadv : p1;
-    issue_w8(w1, p1n);
-    consume8<MT, 32>(w2, xb, acc2, row16, kgrp);
-    const unsigned short* p2n = (ksn < K) ? p2 + kadv : p2;
-    issue_w8(w2, p2n);
-    consume8<MT, 32>(w3, xb, acc3, row16, kgrp);
-    const unsigned short* p3n = (ksn < K) ? p3 + kadv : p3;
-    issue_w8(w3, p3n);
-    p0 = p0n; p1 = p1n; p2 = p2n; p3 = p3n;
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-
-  float* slab = SPLIT ? ws + (long)blockIdx.y * M * N : nullptr;
-#pragma unroll
-  for (int m = 0; m < MT; ++m) {
-    const int mrow = m * 16 + row16;
-    if (mrow >= M) continue;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const long o0 = (long)mrow * N + (nb + 0) * 64 + wid * 16 + 4 * kgrp + r;
-      const long o1 = (long)mrow * N + (nb + 1) * 64 + wid * 16 + 4 * kgrp + r;
-      const long o2 = (long)mrow * N + (nb + 2) * 64 + wid * 16 + 4 * kgrp + r;
-      const long o3 = (long)mrow * N + (nb + 3) * 64 + wid * 16 + 4 * kgrp + r;
-      if (SPLIT) {
-        slab[o0] = acc0[m][r]; slab[o1] = acc1[m][r];
-        slab[o2] = acc2[m][r]; slab[o3] = acc3[m][r];
-      } else {
-        out[o0] = f2us(acc0[m][r]); out[o1] = f2us(acc1[m][r]);
-        out[o2] = f2us(acc2[m][r]); out[o3] = f2us(acc3[m][r]);
       }
     }
   }
@@ -832,377 +812,6 @@ __global__ __launch_bounds__(256) void skinny5_kernel(
   }
 }
 
-void skinny_gemm5(torch::Tensor out, torch::Tensor x, torch::Tensor w,
-                  torch::Tensor ws) {
-  const int M = x.size(0);
-  const long K = x.size(1);
-  const int N = w.size(0);
-  int KS = 128;
-  // KS < 128 is unsound: the XOR swizzle offsets (row&15)<<4 span 256
-  // bytes, a full KS=128 row — at KS=64 they cross rows (measured:
-  // garbage output, sweep_ks.py). 128 and 256 are the valid geometries.
-  if (const char* ov = getenv("KUKEON_SK5_KS")) {
-    KS = atoi(ov) == 256 ? 256 : 128;
-  }
-  TORCH_CHECK(M >= 1 && M <= 64 && N % 128 == 0 && K % KS == 0);
-  TORCH_CHECK(x.is_contiguous() && w.is_contiguous() && out.is_contiguous());
-  TORCH_CHECK(x.scalar_type() == torch::kBFloat16);
-  auto stream = c10::hip::getCurrentHIPStream().stream();
-  // TILES=1 (default): 64 N-cols per block at the same ~256-block
-  // split-K budget -> HALF the slab traffic per block count, measured
-  // 3-4% faster on every dispatched shape (down 31.7 vs 32.6 us,
-  // 70b-down 80.2 vs 83.9 — sweep_nsplit.py; the 512-block
-  // co-residency variant was NOT the win, smaller blocks at equal
-  // splitk were). KUKEON_SK5_NSPLIT=2 restores the two-tile geometry.
-  const char* nv = getenv("KUKEON_SK5_NSPLIT");
-  const int tiles = (nv && atoi(nv) == 2) ? 2 : 1;
-  const int ngroups = N / (tiles * 64);
-  const int nslices = (int)(K / KS);
-  // ~256 blocks: the sweep's knee for every shape — beyond it the
-  // extra split-K slab traffic outweighs occupancy
-  int splitk = 1;
-  if (ngroups < 256)
-    splitk = min(nslices, (256 + ngroups - 1) / ngroups);
-  if (const char* ov = getenv("KUKEON_SK5_SPLITK")) {
-    const int v = atoi(ov);
-    if (v > 0) splitk = min(nslices, v);
-  }
-  const int MT = (M + 15) / 16;
-  dim3 grid(ngroups, splitk);
-  auto* op = reinterpret_cast<unsigned short*>(out.data_ptr());
-  auto* xp = reinterpret_cast<const unsigned short*>(x.data_ptr());
-  auto* wp = reinterpret_cast<const unsigned short*>(w.data_ptr());
-  const long total = (long)M * N;
-#define SK5_LAUNCH_KS(MT_, KS_)                                              \
-  if (splitk == 1 && tiles == 2) {                                           \
-    skinny5_kernel<MT_, false, KS_><<<grid, 256, 0, stream>>>(               \
-        op, nullptr, xp, wp, M, N, K);                                       \
-  } else if (splitk == 1) {                                                  \
-    skinny5_kernel<MT_, false, KS_, false, 1><<<grid, 256, 0, stream>>>(     \
-        op, nullptr, xp, wp, M, N, K);                                       \
-  } else {                                                                   \
-    float* wsp = ws.data_ptr<float>();                                       \
-    TORCH_CHECK(ws.numel() >= total * splitk, "sk5 workspace too small");    \
-    if (tiles == 2) {                                                        \
-      skinny5_kernel<MT_, true, KS_><<<grid, 256, 0, stream>>>(              \
-          nullptr, wsp, xp, wp, M, N, K);                                    \
-    } else {                                                                 \
-      skinny5_kernel<MT_, true, KS_, false, 1><<<grid, 256, 0, stream>>>(    \
-          nullptr, wsp, xp, wp, M, N, K);                                    \
-    }                                                                        \
-    skinny_reduce_kernel<<<dim3((unsigned)((total / 8 + 255) / 256)), 256,   \
-                           0, stream>>>(op, wsp, total, splitk);             \
-  }
-#define SK5_LAUNCH(MT_)                                                      \
-  if (KS == 128) { SK5_LAUNCH_KS(MT_, 128) } else { SK5_LAUNCH_KS(MT_, 256) }
-  switch (MT) {
-    case 1: SK5_LAUNCH(1); break;
-    case 2: SK5_LAUNCH(2); break;
-    case 3: SK5_LAUNCH(3); break;
-    default: SK5_LAUNCH(4); break;
-  }
-#undef SK5_LAUNCH
-#undef SK5_LAUNCH_KS
-  HIP_CHECK_KERNEL();
-}
-
-void skinny_gemm4(torch::Tensor out, torch::Tensor x, torch::Tensor w,
-                  torch::Tensor ws) {
-  const int M = x.size(0);
-  const long K = x.size(1);
-  const int N = w.size(0);
-  TORCH_CHECK(M >= 1 && M <= 64 && N % 256 == 0 && K % KSLICE == 0);
-  TORCH_CHECK(x.is_contiguous() && w.is_contiguous() && out.is_contiguous());
-  TORCH_CHECK(x.scalar_type() == torch::kBFloat16);
-  auto stream = c10::hip::getCurrentHIPStream().stream();
-  const int ngroups = N / 256;
-  const int nslices = (int)(K / KSLICE);
-  int splitk = 1;
-  if (ngroups < 256) splitk = min(nslices, (256 + ngroups - 1) / ngroups);
-  if (const char* ov = getenv("KUKEON_SK4_SPLITK")) {
-    const int v = atoi(ov);
-    if (v > 0) splitk = min(nslices, v);
-  }
-  const int MT = (M + 15) / 16;
-  dim3 grid(ngroups, splitk);
-  auto* op = reinterpret_cast<unsigned short*>(out.data_ptr());
-  auto* xp = reinterpret_cast<const unsigned short*>(x.data_ptr());
-  auto* wp = reinterpret_cast<const unsigned short*>(w.data_ptr());
-  const long total = (long)M * N;
-#define SK4_LAUNCH(MT_)                                                      \
-  if (splitk == 1) {                                                         \
-    skinny4_kernel<MT_, false><<<grid, 256, 0, stream>>>(                    \
-        op, nullptr, xp, wp, M, N, K);                                       \
-  } else {                                                                   \
-    float* wsp = ws.data_ptr<float>();                                       \
-    TORCH_CHECK(ws.numel() >= total * splitk, "sk4 workspace too small");    \
-    skinny4_kernel<MT_, true><<<grid, 256, 0, stream>>>(                     \
-        nullptr, wsp, xp, wp, M, N, K);                                      \
-    skinny_reduce_kernel<<<dim3((unsigned)((total / 8 + 255) / 256)), 256,   \
-                           0, stream>>>(op, wsp, total, splitk);             \
-  }
-  switch (MT) {
-    case 1: SK4_LAUNCH(1); break;
-    case 2: SK4_LAUNCH(2); break;
-    case 3: SK4_LAUNCH(3); break;
-    default: SK4_LAUNCH(4); break;
-  }
-#undef SK4_LAUNCH
-  HIP_CHECK_KERNEL();
-}
-
-void skinny_gemm2(torch::Tensor out, torch::Tensor x, torch::Tensor w,
-                  torch::Tensor ws) {
-  const int M = x.size(0);
-  const long K = x.size(1);
-  const int N = w.size(0);
-  TORCH_CHECK(M >= 1 && M <= 64, "skinny_gemm2: M in [1,64]");
-  TORCH_CHECK(N % 128 == 0 && K % KSLICE == 0,
-              "skinny_gemm2: N%128, K%256");
-  TORCH_CHECK(x.is_contiguous() && w.is_contiguous() && out.is_contiguous());
-  TORCH_CHECK(x.scalar_type() == torch::kBFloat16);
-  auto stream = c10::hip::getCurrentHIPStream().stream();
-  const int ngroups = N / 128;
-  const int nslices = (int)(K / KSLICE);
-  int splitk = 1;
-  if (ngroups < 256) splitk = min(nslices, (256 + ngroups - 1) / ngroups);
-  if (const char* ov = getenv("KUKEON_SK2_SPLITK")) {
-    const int v = atoi(ov);
-    if (v > 0) splitk = min(nslices, v);
-  }
-  const int MT = (M + 15) / 16;
-  dim3 grid(ngroups, splitk);
-  auto* op = reinterpret_cast<unsigned short*>(out.data_ptr());
-  auto* xp = reinterpret_cast<const unsigned short*>(x.data_ptr());
-  auto* wp = reinterpret_cast<const unsigned short*>(w.data_ptr());
-  const long total = (long)M * N;
-#define SK2_LAUNCH(MT_)                                                      \
-  if (splitk == 1) {                                                         \
-    skinny2_kernel<MT_, false, 2><<<grid, 256, 0, stream>>>(                 \
-        op, nullptr, xp, wp, M, N, K);                                       \
-  } else {                                                                   \
-    float* wsp = ws.data_ptr<float>();                                       \
-    TORCH_CHECK(ws.numel() >= total * splitk, "sk2 workspace too small");    \
-    skinny2_kernel<MT_, true, 2><<<grid, 256, 0, stream>>>(                  \
-        nullptr, wsp, xp, wp, M, N, K);                                      \
-    skinny_reduce_kernel<<<dim3((unsigned)((total / 8 + 255) / 256)), 256,   \
-                           0, stream>>>(op, wsp, total, splitk);             \
-  }
-  const char* sm = getenv("KUKEON_SK2_SERIAL");
-  if (sm && MT == 4 && splitk == 1) {
-    const int mask = atoi(sm);
-    switch (mask) {
-      case 1: skinny2_kernel<4, false, 1><<<grid, 256, 0, stream>>>(
-                  op, nullptr, xp, wp, M, N, K); break;
-      case 2: skinny2_kernel<4, false, 2><<<grid, 256, 0, stream>>>(
-                  op, nullptr, xp, wp, M, N, K); break;
-      case 4: skinny2_kernel<4, false, 4><<<grid, 256, 0, stream>>>(
-                  op, nullptr, xp, wp, M, N, K); break;
-      case 8: skinny2_kernel<4, false, 8><<<grid, 256, 0, stream>>>(
-                  op, nullptr, xp, wp, M, N, K); break;
-      case 16: skinny2_kernel<4, false, 16><<<grid, 256, 0, stream>>>(
-                  op, nullptr, xp, wp, M, N, K); break;
-      case 24: skinny2_kernel<4, false, 24><<<grid, 256, 0, stream>>>(
-                  op, nullptr, xp, wp, M, N, K); break;
-      case 34: skinny2_kernel<4, false, 34><<<grid, 256, 0, stream>>>(
-                  op, nullptr, xp, wp, M, N, K); break;
-      case 42: skinny2_kernel<4, false, 42><<<grid, 256, 0, stream>>>(
-                  op, nullptr, xp, wp, M, N, K); break;
-      case 10: skinny2_kernel<4, false, 10><<<grid, 256, 0, stream>>>(
-                  op, nullptr, xp, wp, M, N, K); break;
-      default: skinny2_kernel<4, false, 7><<<grid, 256, 0, stream>>>(
-                  op, nullptr, xp, wp, M, N, K); break;
-    }
-    HIP_CHECK_KERNEL();
-    return;
-  }
-  switch (MT) {
-    case 1: SK2_LAUNCH(1); break;
-    case 2: SK2_LAUNCH(2); break;
-    case 3: SK2_LAUNCH(3); break;
-    default: SK2_LAUNCH(4); break;
-  }
-#undef SK2_LAUNCH
-  HIP_CHECK_KERNEL();
-}
-
-// reduce the split-K slabs and cast to bf16
-__global__ void skinny_reduce_kernel(unsigned short* __restrict__ out,
-                                     const float* __restrict__ ws, long n,
-                                     int splitk) {
-  const long i = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 8;
-  if (i + 7 < n) {
-    float v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    for (int s = 0; s < splitk; ++s) {
-      const float4 a = *reinterpret_cast<const float4*>(ws + s * n + i);
-      const float4 b = *reinterpret_cast<const float4*>(ws + s * n + i + 4);
-      v[0] += a.x; v[1] += a.y; v[2] += a.z; v[3] += a.w;
-      v[4] += b.x; v[5] += b.y; v[6] += b.z; v[7] += b.w;
-    }
-    *reinterpret_cast<uint4*>(out + i) = pack_bf16x8(v);
-  } else {
-    for (long j = i; j < n; ++j) {
-      float acc = 0.f;
-      for (int s = 0; s < splitk; ++s) acc += ws[s * n + j];
-      out[j] = f2us(acc);
-    }
-  }
-}
-
-// Split-K reduce fused with residual-add + RMSNorm: the decode o-proj's
-// epilogue pair (skinny_reduce 5.0us + fused_add_rmsnorm 5.4us) was two
-// launches at the ~4.5us in-graph dispatch floor each for <1us of real
-// work. One block per row: sum the slabs, update the residual in place,
-// one block-reduce for the mean square, write the normed activations.
-__global__ __launch_bounds__(256) void skinny_reduce_add_rmsnorm_kernel(
-    unsigned short* __restrict__ normed,    // [M, N] bf16
-    unsigned short* __restrict__ residual,  // [M, N] bf16, updated
-    const float* __restrict__ ws,           // [splitk, M, N] f32
-    const unsigned short* __restrict__ nw,  // [N]
-    int N, long total, int splitk, float eps) {
-  const int t = blockIdx.x;
-  __shared__ float red[16];
-  float vals[32];  // up to N = 8192 at 256 threads x 8 elems
-  const int nchunk = N / (256 * 8);
-  float sq = 0.f;
-  for (int c = 0; c < nchunk; ++c) {
-    const int n0 = (c * 256 + threadIdx.x) * 8;
-    const long off = (long)t * N + n0;
-    const bf16x8 r = load_bf16x8(residual + off);
-    float acc[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) acc[j] = r.f(j);
-    for (int s = 0; s < splitk; ++s) {
-      const float4 a =
-          *reinterpret_cast<const float4*>(ws + (long)s * total + off);
-      const float4 b =
-          *reinterpret_cast<const float4*>(ws + (long)s * total + off + 4);
-      acc[0] += a.x; acc[1] += a.y; acc[2] += a.z; acc[3] += a.w;
-      acc[4] += b.x; acc[5] += b.y; acc[6] += b.z; acc[7] += b.w;
-    }
-    *reinterpret_cast<uint4*>(residual + off) = pack_bf16x8(acc);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      // norm of the bf16-rounded residual, matching the two-kernel path
-      const float v = us2f(f2us(acc[j]));
-      vals[c * 8 + j] = v;
-      sq += v * v;
-    }
-  }
-  sq = block_reduce(sq, red, SumOp{}, 0.f);
-  const float rs = __frsqrt_rn(sq / N + eps);
-  for (int c = 0; c < nchunk; ++c) {
-    const int n0 = (c * 256 + threadIdx.x) * 8;
-    const bf16x8 wv = load_bf16x8(nw + n0);
-    float o[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) o[j] = vals[c * 8 + j] * rs * wv.f(j);
-    *reinterpret_cast<uint4*>(normed + (long)t * N + n0) = pack_bf16x8(o);
-  }
-}
-
-void skinny_gemm_fused_norm(torch::Tensor normed, torch::Tensor x,
-                            torch::Tensor w, torch::Tensor ws,
-                            torch::Tensor residual, torch::Tensor nw,
-                            double eps) {
-  const int M = x.size(0);
-  const long K = x.size(1);
-  const int N = w.size(0);
-  TORCH_CHECK(M >= 1 && M <= 64 && N % 2048 == 0 && N <= 8192 &&
-              K % 32 == 0);
-  TORCH_CHECK(x.is_contiguous() && w.is_contiguous() &&
-              residual.is_contiguous() && normed.is_contiguous());
-  auto stream = c10::hip::getCurrentHIPStream().stream();
-  const int ntiles = N / 64;
-  const int nslices = (int)((K + KSLICE - 1) / KSLICE);
-  int splitk = min(nslices, (256 + ntiles - 1) / ntiles);
-  if (const char* ov = getenv("KUKEON_SKINNY_SPLITK")) {
-    const int v = atoi(ov);
-    if (v > 0) splitk = min(nslices, v);
-  }
-  const int MT = (M + 15) / 16;
-  dim3 grid(ntiles, splitk);
-  auto* xp = reinterpret_cast<const unsigned short*>(x.data_ptr());
-  auto* wp = reinterpret_cast<const unsigned short*>(w.data_ptr());
-  const long total = (long)M * N;
-  float* wsp = ws.data_ptr<float>();
-  TORCH_CHECK(ws.numel() >= total * splitk, "workspace too small");
-#define SKF_LAUNCH(MT_)                                                      \
-  skinny_gemm_kernel<MT_, true><<<grid, 256, 0, stream>>>(                   \
-      nullptr, wsp, xp, wp, M, N, K)
-  switch (MT) {
-    case 1: SKF_LAUNCH(1); break;
-    case 2: SKF_LAUNCH(2); break;
-    case 3: SKF_LAUNCH(3); break;
-    default: SKF_LAUNCH(4); break;
-  }
-#undef SKF_LAUNCH
-  HIP_CHECK_KERNEL();
-  skinny_reduce_add_rmsnorm_kernel<<<dim3((unsigned)M), 256, 0, stream>>>(
-      reinterpret_cast<unsigned short*>(normed.data_ptr()),
-      reinterpret_cast<unsigned short*>(residual.data_ptr()), wsp,
-      reinterpret_cast<const unsigned short*>(nw.data_ptr()), N, total,
-      splitk, (float)eps);
-  HIP_CHECK_KERNEL();
-}
-
-void skinny_gemm5_fused_norm(torch::Tensor normed, torch::Tensor x,
-                             torch::Tensor w, torch::Tensor ws,
-                             torch::Tensor residual, torch::Tensor nw,
-                             double eps) {
-  // skinny5 (full-line never-drain pipeline) + the split-K reduce fused
-  // with residual add + RMSNorm: the decode down-projection epilogue in
-  // ONE kernel instead of reduce + norm (two ~4.5us in-graph launches).
-  const int M = x.size(0);
-  const long K = x.size(1);
-  const int N = w.size(0);
-  constexpr int KS = 128;
-  TORCH_CHECK(M >= 1 && M <= 64 && N % 2048 == 0 && N <= 8192 &&
-              K % KS == 0);
-  TORCH_CHECK(x.is_contiguous() && w.is_contiguous() &&
-              residual.is_contiguous() && normed.is_contiguous());
-  auto stream = c10::hip::getCurrentHIPStream().stream();
-  const char* nv = getenv("KUKEON_SK5_NSPLIT");
-  const int tiles = (nv && atoi(nv) == 2) ? 2 : 1;   // see skinny_gemm5
-  const int ngroups = N / (tiles * 64);
-  const int nslices = (int)(K / KS);
-  int splitk = min(nslices, (256 + ngroups - 1) / ngroups);
-  if (const char* ov = getenv("KUKEON_SK5_SPLITK")) {
-    const int v = atoi(ov);
-    if (v > 0) splitk = min(nslices, v);
-  }
-  const int MT = (M + 15) / 16;
-  dim3 grid(ngroups, splitk);
-  auto* xp = reinterpret_cast<const unsigned short*>(x.data_ptr());
-  auto* wp = reinterpret_cast<const unsigned short*>(w.data_ptr());
-  const long total = (long)M * N;
-  float* wsp = ws.data_ptr<float>();
-  TORCH_CHECK(ws.numel() >= total * splitk, "workspace too small");
-#define SK5F_LAUNCH(MT_)                                                    \
-  if (tiles == 2) {                                                         \
-    skinny5_kernel<MT_, true, KS><<<grid, 256, 0, stream>>>(                \
-        nullptr, wsp, xp, wp, M, N, K);                                     \
-  } else {                                                                  \
-    skinny5_kernel<MT_, true, KS, false, 1><<<grid, 256, 0, stream>>>(      \
-        nullptr, wsp, xp, wp, M, N, K);                                     \
-  }
-  switch (MT) {
-    case 1: SK5F_LAUNCH(1); break;
-    case 2: SK5F_LAUNCH(2); break;
-    case 3: SK5F_LAUNCH(3); break;
-    default: SK5F_LAUNCH(4); break;
-  }
-#undef SK5F_LAUNCH
-  HIP_CHECK_KERNEL();
-  skinny_reduce_add_rmsnorm_kernel<<<dim3((unsigned)M), 256, 0, stream>>>(
-      reinterpret_cast<unsigned short*>(normed.data_ptr()),
-      reinterpret_cast<unsigned short*>(residual.data_ptr()), wsp,
-      reinterpret_cast<const unsigned short*>(nw.data_ptr()), N, total,
-      splitk, (float)eps);
-  HIP_CHECK_KERNEL();
-}
-
-
 // ---------------------------------------------------------------------------
 // v6: barrier-free register-x pipeline.
 //
@@ -1360,217 +969,297 @@ __global__ __launch_bounds__(256) void skinny6_kernel(
   }
 }
 
-void skinny_gemm5_silu_fused_norm(torch::Tensor normed, torch::Tensor gu,
-                                  torch::Tensor w, torch::Tensor ws,
-                                  torch::Tensor residual, torch::Tensor nw,
-                                  double eps) {
-  // The whole decode MLP tail in two kernels: silu(gate)*up happens in
-  // registers inside the down-projection's x staging (SILU template
-  // path), and the split-K reduce fuses with the next layer's residual
-  // add + RMSNorm. Measured SLOWER than silu_mul + skinny_gemm5 in situ
-  // (54.2 vs 42.9 us cold — doubling the x-staging bytes beats the
-  // saved launch; ledger profiles/r02_progress.md) so dispatch is off
-  // by default (KUKEON_FUSE_SILU=1 re-enables); kept as the documented
-  // negative result.
-  const int M = gu.size(0);
-  const int N = w.size(0);
-  const long K = w.size(1);
-  constexpr int KS = 128;
-  TORCH_CHECK(M >= 1 && M <= 64 && N % 2048 == 0 && N <= 8192 &&
-              K % KS == 0);
-  TORCH_CHECK(gu.size(1) == 2 * K, "gate_up output must be [M, 2K]");
-  TORCH_CHECK(gu.is_contiguous() && w.is_contiguous() &&
-              residual.is_contiguous() && normed.is_contiguous());
-  TORCH_CHECK(gu.scalar_type() == torch::kBFloat16);
-  auto stream = c10::hip::getCurrentHIPStream().stream();
-  const char* nv = getenv("KUKEON_SK5_NSPLIT");
-  const int tiles = (nv && atoi(nv) == 2) ? 2 : 1;   // see skinny_gemm5
-  const int ngroups = N / (tiles * 64);
-  const int nslices = (int)(K / KS);
-  int splitk = min(nslices, (256 + ngroups - 1) / ngroups);
-  if (const char* ov = getenv("KUKEON_SK5_SPLITK")) {
+// ===========================================================================
+// Host side. Every variant is the same algorithm: split K over ~256 blocks,
+// run the GEMM kernel straight to bf16 (splitk == 1) or into splitk f32
+// slabs, then one of two epilogues. A variant differs only in its plan
+// parameters and its kernel.
+// ===========================================================================
+
+struct SkinnyPlan {
+  int M, N;
+  long K;
+  int ngroups;  // grid.x: blocks along N
+  int nslices;  // K slices available to split over
+  int splitk;   // grid.y: f32 slabs written when > 1
+  int MT;       // 16-row M subtiles
+};
+
+// ~256 blocks (1x the CU count) is the sweep's knee for every shape:
+// per-block latency is ~constant in N in this regime, so more split-K
+// past chip fill only adds slab/reduce traffic (scripts/sweep_splitk.py).
+// At `off_at` blocks or more along N the grid fills the chip by itself.
+static SkinnyPlan skinny_plan(int M, int N, long K, int cols, int slice,
+                              int off_at, const char* env) {
+  SkinnyPlan p{M, N, K};
+  p.ngroups = N / cols;
+  TORCH_CHECK(p.ngroups > 0, "skinny plan: N < ", cols);
+  p.nslices = (int)((K + slice - 1) / slice);
+  p.splitk = p.ngroups >= off_at
+                 ? 1
+                 : min(p.nslices, (256 + p.ngroups - 1) / p.ngroups);
+  if (const char* ov = getenv(env)) {
     const int v = atoi(ov);
-    if (v > 0) splitk = min(nslices, v);
+    if (v > 0) p.splitk = min(p.nslices, v);
   }
-  const int MT = (M + 15) / 16;
-  dim3 grid(ngroups, splitk);
-  auto* xp = reinterpret_cast<const unsigned short*>(gu.data_ptr());
-  auto* wp = reinterpret_cast<const unsigned short*>(w.data_ptr());
-  const long total = (long)M * N;
-  float* wsp = ws.data_ptr<float>();
-  TORCH_CHECK(ws.numel() >= total * splitk, "workspace too small");
-#define SK5S_LAUNCH(MT_)                                                    \
-  if (tiles == 2) {                                                         \
-    skinny5_kernel<MT_, true, KS, true><<<grid, 256, 0, stream>>>(          \
-        nullptr, wsp, xp, wp, M, N, K);                                     \
-  } else {                                                                  \
-    skinny5_kernel<MT_, true, KS, true, 1><<<grid, 256, 0, stream>>>(       \
-        nullptr, wsp, xp, wp, M, N, K);                                     \
-  }
+  p.MT = (M + 15) / 16;
+  return p;
+}
+
+// TILES=1 (default): 64 N-cols per block at the same ~256-block split-K
+// budget -> HALF the slab traffic per block count, measured 3-4% faster
+// on every dispatched shape (down 31.7 vs 32.6 us, 70b-down 80.2 vs 83.9
+// — sweep_nsplit.py; the 512-block co-residency variant was NOT the win,
+// smaller blocks at equal splitk were). KUKEON_SK5_NSPLIT=2 restores the
+// two-tile geometry.
+static int sk5_tiles() {
+  const char* nv = getenv("KUKEON_SK5_NSPLIT");
+  return (nv && atoi(nv) == 2) ? 2 : 1;
+}
+
+// KS < 128 is unsound: the XOR swizzle offsets (row&15)<<4 span 256
+// bytes, a full KS=128 row — at KS=64 they cross rows (measured: garbage
+// output, sweep_ks.py). 128 and 256 are the valid geometries.
+static int ks_from_env(const char* env) {
+  const char* ov = getenv(env);
+  return (ov && atoi(ov) == 256) ? 256 : 128;
+}
+
+static SkinnyPlan plan_v1(int M, int N, long K) {
+  return skinny_plan(M, N, K, 64, KSLICE, 512, "KUKEON_SKINNY_SPLITK");
+}
+static SkinnyPlan plan_v2(int M, int N, long K) {
+  return skinny_plan(M, N, K, 128, KSLICE, 256, "KUKEON_SK2_SPLITK");
+}
+static SkinnyPlan plan_v5(int M, int N, long K, int tiles, int KS) {
+  return skinny_plan(M, N, K, 64 * tiles, KS, 256, "KUKEON_SK5_SPLITK");
+}
+static SkinnyPlan plan_v6(int M, int N, long K, int KS) {
+  return skinny_plan(M, N, K, 128, KS, 256, "KUKEON_SK6_SPLITK");
+}
+
+// The split-K factor a launcher will use, for sizing its workspace
+// (64 * N * splitk floats cover every M). Host-only.
+int64_t skinny_splitk(const std::string& kind, int64_t N, int64_t K) {
+  const int n = (int)N;
+  if (kind == "v1") return plan_v1(1, n, K).splitk;
+  if (kind == "v2") return plan_v2(1, n, K).splitk;
+  if (kind == "v5")
+    return plan_v5(1, n, K, sk5_tiles(), ks_from_env("KUKEON_SK5_KS")).splitk;
+  if (kind == "v5_fused") return plan_v5(1, n, K, sk5_tiles(), 128).splitk;
+  if (kind == "v6")
+    return plan_v6(1, n, K, ks_from_env("KUKEON_SK6_KS")).splitk;
+  TORCH_CHECK(false, "skinny_splitk: unknown kind ", kind);
+}
+
+using SkinnyKernel = void (*)(unsigned short*, float*, const unsigned short*,
+                              const unsigned short*, int, int, long);
+
+// f(std::integral_constant<int, MT>) with the runtime MT as a constant
+template <class F>
+static void with_mt(int MT, F&& f) {
   switch (MT) {
-    case 1: SK5S_LAUNCH(1); break;
-    case 2: SK5S_LAUNCH(2); break;
-    case 3: SK5S_LAUNCH(3); break;
-    default: SK5S_LAUNCH(4); break;
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 3: f(std::integral_constant<int, 3>{}); break;
+    default: f(std::integral_constant<int, 4>{}); break;
   }
-#undef SK5S_LAUNCH
-  HIP_CHECK_KERNEL();
-  skinny_reduce_add_rmsnorm_kernel<<<dim3((unsigned)M), 256, 0, stream>>>(
-      reinterpret_cast<unsigned short*>(normed.data_ptr()),
-      reinterpret_cast<unsigned short*>(residual.data_ptr()), wsp,
-      reinterpret_cast<const unsigned short*>(nw.data_ptr()), N, total,
-      splitk, (float)eps);
+}
+
+static unsigned short* us_ptr(const torch::Tensor& t) {
+  return reinterpret_cast<unsigned short*>(t.data_ptr());
+}
+
+static float* slab_ptr(const SkinnyPlan& p, torch::Tensor& ws) {
+  TORCH_CHECK(ws.numel() >= (long)p.M * p.N * p.splitk,
+              "skinny workspace too small");
+  return ws.data_ptr<float>();
+}
+
+// Plain epilogue: `direct` writes bf16 itself at splitk == 1; otherwise
+// `split` fills the slabs and the reduce pass casts their sum to bf16.
+static void run_reduce(const SkinnyPlan& p, SkinnyKernel direct,
+                       SkinnyKernel split, torch::Tensor& out,
+                       const torch::Tensor& x, const torch::Tensor& w,
+                       torch::Tensor& ws) {
+  auto stream = c10::hip::getCurrentHIPStream().stream();
+  const dim3 grid(p.ngroups, p.splitk);
+  if (p.splitk == 1) {
+    direct<<<grid, 256, 0, stream>>>(us_ptr(out), nullptr, us_ptr(x),
+                                     us_ptr(w), p.M, p.N, p.K);
+  } else {
+    float* wsp = slab_ptr(p, ws);
+    const long total = (long)p.M * p.N;
+    split<<<grid, 256, 0, stream>>>(nullptr, wsp, us_ptr(x), us_ptr(w), p.M,
+                                    p.N, p.K);
+    skinny_reduce_kernel<<<dim3((unsigned)((total / 8 + 255) / 256)), 256, 0,
+                           stream>>>(us_ptr(out), wsp, total, p.splitk);
+  }
   HIP_CHECK_KERNEL();
 }
 
-void skinny_gemm6(torch::Tensor out, torch::Tensor x, torch::Tensor w,
-                  torch::Tensor ws) {
-  const int M = x.size(0);
-  const long K = x.size(1);
-  const int N = w.size(0);
-  int KS = 128;
-  if (const char* ov = getenv("KUKEON_SK6_KS")) {
-    KS = atoi(ov) == 256 ? 256 : 128;
-  }
-  TORCH_CHECK(M >= 1 && M <= 64 && N % 128 == 0 && K % KS == 0);
+// Fused epilogue: always the slab kernel (also at splitk == 1), then
+// split-K reduce + residual add + RMSNorm in one kernel.
+static void run_reduce_add_rmsnorm(const SkinnyPlan& p, SkinnyKernel split,
+                                   torch::Tensor& normed,
+                                   const torch::Tensor& x,
+                                   const torch::Tensor& w, torch::Tensor& ws,
+                                   torch::Tensor& residual,
+                                   const torch::Tensor& nw, double eps) {
+  auto stream = c10::hip::getCurrentHIPStream().stream();
+  float* wsp = slab_ptr(p, ws);
+  split<<<dim3(p.ngroups, p.splitk), 256, 0, stream>>>(
+      nullptr, wsp, us_ptr(x), us_ptr(w), p.M, p.N, p.K);
+  HIP_CHECK_KERNEL();
+  skinny_reduce_add_rmsnorm_kernel<<<dim3((unsigned)p.M), 256, 0, stream>>>(
+      us_ptr(normed), us_ptr(residual), wsp, us_ptr(nw), p.N,
+      (long)p.M * p.N, p.splitk, (float)eps);
+  HIP_CHECK_KERNEL();
+}
+
+// shape checks shared by the plain / fused entry points (the fused
+// epilogue holds one row in 32 registers per thread: N <= 8192, N%2048)
+static void check_plain(const torch::Tensor& out, const torch::Tensor& x,
+                        const torch::Tensor& w, int ncols, int kdiv) {
+  const long M = x.size(0);
+  TORCH_CHECK(M >= 1 && M <= 64, "skinny gemm: M must be in [1,64]");
+  TORCH_CHECK(w.size(0) % ncols == 0 && x.size(1) % kdiv == 0,
+              "skinny gemm: N%", ncols, ", K%", kdiv);
   TORCH_CHECK(x.is_contiguous() && w.is_contiguous() && out.is_contiguous());
   TORCH_CHECK(x.scalar_type() == torch::kBFloat16);
-  auto stream = c10::hip::getCurrentHIPStream().stream();
-  const int ngroups = N / 128;
-  const int nslices = (int)(K / KS);
-  int splitk = 1;
-  if (ngroups < 256)
-    splitk = min(nslices, (256 + ngroups - 1) / ngroups);
-  if (const char* ov = getenv("KUKEON_SK6_SPLITK")) {
-    const int v = atoi(ov);
-    if (v > 0) splitk = min(nslices, v);
-  }
-  const int MT = (M + 15) / 16;
-  dim3 grid(ngroups, splitk);
-  auto* op = reinterpret_cast<unsigned short*>(out.data_ptr());
-  auto* xp = reinterpret_cast<const unsigned short*>(x.data_ptr());
-  auto* wp = reinterpret_cast<const unsigned short*>(w.data_ptr());
-  const long total = (long)M * N;
-#define SK6_LAUNCH_KS(MT_, KS_)                                              \
-  if (splitk == 1) {                                                         \
-    skinny6_kernel<MT_, false, KS_><<<grid, 256, 0, stream>>>(               \
-        op, nullptr, xp, wp, M, N, K);                                       \
-  } else {                                                                   \
-    float* wsp = ws.data_ptr<float>();                                       \
-    TORCH_CHECK(ws.numel() >= total * splitk, "sk6 workspace too small");    \
-    skinny6_kernel<MT_, true, KS_><<<grid, 256, 0, stream>>>(                \
-        nullptr, wsp, xp, wp, M, N, K);                                      \
-    skinny_reduce_kernel<<<dim3((unsigned)((total / 8 + 255) / 256)), 256,   \
-                           0, stream>>>(op, wsp, total, splitk);             \
-  }
-#define SK6_LAUNCH(MT_)                                                      \
-  if (KS == 128) { SK6_LAUNCH_KS(MT_, 128) } else { SK6_LAUNCH_KS(MT_, 256) }
-  switch (MT) {
-    case 1: SK6_LAUNCH(1); break;
-    case 2: SK6_LAUNCH(2); break;
-    case 3: SK6_LAUNCH(3); break;
-    default: SK6_LAUNCH(4); break;
-  }
-#undef SK6_LAUNCH
-#undef SK6_LAUNCH_KS
-  HIP_CHECK_KERNEL();
 }
-
-void skinny_gemm6_fused_norm(torch::Tensor normed, torch::Tensor x,
-                             torch::Tensor w, torch::Tensor ws,
-                             torch::Tensor residual, torch::Tensor nw,
-                             double eps) {
-  const int M = x.size(0);
-  const long K = x.size(1);
-  const int N = w.size(0);
-  constexpr int KS = 128;
+static void check_fused(const torch::Tensor& normed, const torch::Tensor& x,
+                        const torch::Tensor& w, const torch::Tensor& residual,
+                        long K, int kdiv) {
+  const long M = x.size(0), N = w.size(0);
   TORCH_CHECK(M >= 1 && M <= 64 && N % 2048 == 0 && N <= 8192 &&
-              K % KS == 0);
+              K % kdiv == 0);
   TORCH_CHECK(x.is_contiguous() && w.is_contiguous() &&
               residual.is_contiguous() && normed.is_contiguous());
-  auto stream = c10::hip::getCurrentHIPStream().stream();
-  const int ngroups = N / 128;
-  const int nslices = (int)(K / KS);
-  int splitk = min(nslices, (256 + ngroups - 1) / ngroups);
-  if (const char* ov = getenv("KUKEON_SK6_SPLITK")) {
-    const int v = atoi(ov);
-    if (v > 0) splitk = min(nslices, v);
-  }
-  const int MT = (M + 15) / 16;
-  dim3 grid(ngroups, splitk);
-  auto* xp = reinterpret_cast<const unsigned short*>(x.data_ptr());
-  auto* wp = reinterpret_cast<const unsigned short*>(w.data_ptr());
-  const long total = (long)M * N;
-  float* wsp = ws.data_ptr<float>();
-  TORCH_CHECK(ws.numel() >= total * splitk, "workspace too small");
-#define SK6F_LAUNCH(MT_)                                                    \
-  skinny6_kernel<MT_, true, KS><<<grid, 256, 0, stream>>>(                  \
-      nullptr, wsp, xp, wp, M, N, K)
-  switch (MT) {
-    case 1: SK6F_LAUNCH(1); break;
-    case 2: SK6F_LAUNCH(2); break;
-    case 3: SK6F_LAUNCH(3); break;
-    default: SK6F_LAUNCH(4); break;
-  }
-#undef SK6F_LAUNCH
-  HIP_CHECK_KERNEL();
-  skinny_reduce_add_rmsnorm_kernel<<<dim3((unsigned)M), 256, 0, stream>>>(
-      reinterpret_cast<unsigned short*>(normed.data_ptr()),
-      reinterpret_cast<unsigned short*>(residual.data_ptr()), wsp,
-      reinterpret_cast<const unsigned short*>(nw.data_ptr()), N, total,
-      splitk, (float)eps);
-  HIP_CHECK_KERNEL();
+}
+
+template <int MT, bool SPLIT, int KS, bool SILU>
+static SkinnyKernel sk5_kernel(int tiles) {
+  return tiles == 2 ? skinny5_kernel<MT, SPLIT, KS, SILU, 2>
+                    : skinny5_kernel<MT, SPLIT, KS, SILU, 1>;
 }
 
 void skinny_gemm(torch::Tensor out, torch::Tensor x, torch::Tensor w,
                  torch::Tensor ws) {
-  const int M = x.size(0);
-  const long K = x.size(1);
-  const int N = w.size(0);
-  TORCH_CHECK(M >= 1 && M <= 64, "skinny_gemm: M must be in [1,64]");
-  TORCH_CHECK(N % 64 == 0 && K % 32 == 0, "skinny_gemm: N%64, K%32");
-  TORCH_CHECK(x.is_contiguous() && w.is_contiguous() && out.is_contiguous());
-  TORCH_CHECK(x.scalar_type() == torch::kBFloat16);
-  auto stream = c10::hip::getCurrentHIPStream().stream();
-  const int ntiles = N / 64;
-  const int nslices = (int)((K + KSLICE - 1) / KSLICE);
-  // decomposition targets ~256 blocks (1x the CU count): per-block
-  // latency is ~constant in N in this regime, so more split-K past chip
-  // fill only adds reduce traffic (measured in scripts/sweep_splitk.py)
-  int splitk = 1;
-  if (ntiles < 512) splitk = min(nslices, (256 + ntiles - 1) / ntiles);
-  if (const char* ov = getenv("KUKEON_SKINNY_SPLITK")) {
-    const int v = atoi(ov);
-    if (v > 0) splitk = min(nslices, v);
-  }
-  const int MT = (M + 15) / 16;
-  dim3 grid(ntiles, splitk);
-  auto* op = reinterpret_cast<unsigned short*>(out.data_ptr());
-  auto* xp = reinterpret_cast<const unsigned short*>(x.data_ptr());
-  auto* wp = reinterpret_cast<const unsigned short*>(w.data_ptr());
-  const long total = (long)M * N;
+  check_plain(out, x, w, 64, 32);
+  const SkinnyPlan p = plan_v1(x.size(0), w.size(0), x.size(1));
+  SkinnyKernel direct = nullptr, split = nullptr;
+  with_mt(p.MT, [&](auto mt) {
+    constexpr int MT = decltype(mt)::value;
+    direct = skinny_gemm_kernel<MT, false>;
+    split = skinny_gemm_kernel<MT, true>;
+  });
+  run_reduce(p, direct, split, out, x, w, ws);
+}
 
-#define SK_LAUNCH(MT_)                                                       \
-  if (splitk == 1) {                                                         \
-    skinny_gemm_kernel<MT_, false><<<grid, 256, 0, stream>>>(                \
-        op, nullptr, xp, wp, M, N, K);                                       \
-  } else {                                                                   \
-    float* wsp = ws.data_ptr<float>();                                       \
-    TORCH_CHECK(ws.numel() >= total * splitk,                                \
-                "skinny_gemm workspace too small");                          \
-    skinny_gemm_kernel<MT_, true><<<grid, 256, 0, stream>>>(                 \
-        nullptr, wsp, xp, wp, M, N, K);                                      \
-    skinny_reduce_kernel<<<dim3((unsigned)((total / 8 + 255) / 256)), 256,   \
-                           0, stream>>>(op, wsp, total, splitk);             \
-  }
-  switch (MT) {
-    case 1: SK_LAUNCH(1); break;
-    case 2: SK_LAUNCH(2); break;
-    case 3: SK_LAUNCH(3); break;
-    default: SK_LAUNCH(4); break;
-  }
-#undef SK_LAUNCH
-  HIP_CHECK_KERNEL();
+void skinny_gemm_fused_norm(torch::Tensor normed, torch::Tensor x,
+                            torch::Tensor w, torch::Tensor ws,
+                            torch::Tensor residual, torch::Tensor nw,
+                            double eps) {
+  check_fused(normed, x, w, residual, x.size(1), 32);
+  const SkinnyPlan p = plan_v1(x.size(0), w.size(0), x.size(1));
+  SkinnyKernel split = nullptr;
+  with_mt(p.MT, [&](auto mt) {
+    split = skinny_gemm_kernel<decltype(mt)::value, true>;
+  });
+  run_reduce_add_rmsnorm(p, split, normed, x, w, ws, residual, nw, eps);
+}
+
+void skinny_gemm2(torch::Tensor out, torch::Tensor x, torch::Tensor w,
+                  torch::Tensor ws) {
+  check_plain(out, x, w, 128, KSLICE);
+  const SkinnyPlan p = plan_v2(x.size(0), w.size(0), x.size(1));
+  SkinnyKernel direct = nullptr, split = nullptr;
+  with_mt(p.MT, [&](auto mt) {
+    constexpr int MT = decltype(mt)::value;
+    direct = skinny2_kernel<MT, false>;
+    split = skinny2_kernel<MT, true>;
+  });
+  run_reduce(p, direct, split, out, x, w, ws);
+}
+
+void skinny_gemm5(torch::Tensor out, torch::Tensor x, torch::Tensor w,
+                  torch::Tensor ws) {
+  const int KS = ks_from_env("KUKEON_SK5_KS");
+  const int tiles = sk5_tiles();
+  check_plain(out, x, w, 128, KS);
+  const SkinnyPlan p = plan_v5(x.size(0), w.size(0), x.size(1), tiles, KS);
+  SkinnyKernel direct = nullptr, split = nullptr;
+  with_mt(p.MT, [&](auto mt) {
+    constexpr int MT = decltype(mt)::value;
+    if (KS == 128) {
+      direct = sk5_kernel<MT, false, 128, false>(tiles);
+      split = sk5_kernel<MT, true, 128, false>(tiles);
+    } else {
+      direct = sk5_kernel<MT, false, 256, false>(tiles);
+      split = sk5_kernel<MT, true, 256, false>(tiles);
+    }
+  });
+  run_reduce(p, direct, split, out, x, w, ws);
+}
+
+// skinny5 + the split-K reduce fused with residual add + RMSNorm: the
+// decode down-projection epilogue in ONE kernel instead of reduce + norm
+// (two ~4.5us in-graph launches).
+void skinny_gemm5_fused_norm(torch::Tensor normed, torch::Tensor x,
+                             torch::Tensor w, torch::Tensor ws,
+                             torch::Tensor residual, torch::Tensor nw,
+                             double eps) {
+  check_fused(normed, x, w, residual, x.size(1), 128);
+  const int tiles = sk5_tiles();
+  const SkinnyPlan p = plan_v5(x.size(0), w.size(0), x.size(1), tiles, 128);
+  SkinnyKernel split = nullptr;
+  with_mt(p.MT, [&](auto mt) {
+    split = sk5_kernel<decltype(mt)::value, true, 128, false>(tiles);
+  });
+  run_reduce_add_rmsnorm(p, split, normed, x, w, ws, residual, nw, eps);
+}
+
+// The whole decode MLP tail in two kernels: silu(gate)*up happens in
+// registers inside the down-projection's x staging (SILU template path),
+// and the split-K reduce fuses with the next layer's residual add +
+// RMSNorm. Measured SLOWER than silu_mul + skinny_gemm5 in situ (54.2 vs
+// 42.9 us cold — doubling the x-staging bytes beats the saved launch;
+// ledger profiles/r02_progress.md) so dispatch is off by default
+// (KUKEON_FUSE_SILU=1 re-enables); kept as the documented negative result.
+void skinny_gemm5_silu_fused_norm(torch::Tensor normed, torch::Tensor gu,
+                                  torch::Tensor w, torch::Tensor ws,
+                                  torch::Tensor residual, torch::Tensor nw,
+                                  double eps) {
+  check_fused(normed, gu, w, residual, w.size(1), 128);
+  TORCH_CHECK(gu.size(1) == 2 * w.size(1), "gate_up output must be [M, 2K]");
+  TORCH_CHECK(gu.scalar_type() == torch::kBFloat16);
+  const int tiles = sk5_tiles();
+  const SkinnyPlan p = plan_v5(gu.size(0), w.size(0), w.size(1), tiles, 128);
+  SkinnyKernel split = nullptr;
+  with_mt(p.MT, [&](auto mt) {
+    split = sk5_kernel<decltype(mt)::value, true, 128, true>(tiles);
+  });
+  run_reduce_add_rmsnorm(p, split, normed, gu, w, ws, residual, nw, eps);
+}
+
+void skinny_gemm6(torch::Tensor out, torch::Tensor x, torch::Tensor w,
+                  torch::Tensor ws) {
+  const int KS = ks_from_env("KUKEON_SK6_KS");
+  check_plain(out, x, w, 128, KS);
+  const SkinnyPlan p = plan_v6(x.size(0), w.size(0), x.size(1), KS);
+  SkinnyKernel direct = nullptr, split = nullptr;
+  with_mt(p.MT, [&](auto mt) {
+    constexpr int MT = decltype(mt)::value;
+    if (KS == 128) {
+      direct = skinny6_kernel<MT, false, 128>;
+      split = skinny6_kernel<MT, true, 128>;
+    } else {
+      direct = skinny6_kernel<MT, false, 256>;
+      split = skinny6_kernel<MT, true, 256>;
+    }
+  });
+  run_reduce(p, direct, split, out, x, w, ws);
 }
 
 }  // namespace kukeon

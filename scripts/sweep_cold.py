@@ -77,13 +77,4 @@ for (M, N, K, tag) in SHAPES:
             line += f"  v5-{ks}k{sk or 'A'}={us:6.1f}"
         os.environ.pop("KUKEON_SK5_SPLITK", None)
     os.environ.pop("KUKEON_SK5_KS", None)
-    if N % 256 == 0:
-        for sk in (0, 2, 4, 8, 16):
-            if sk:
-                os.environ["KUKEON_SK4_SPLITK"] = str(sk)
-            else:
-                os.environ.pop("KUKEON_SK4_SPLITK", None)
-            us = t_rot(lambda i: _C.skinny_gemm4(out, x, ws_list[i], wrk), nw)
-            line += f"  v4k{sk or 'A'}={us:6.1f}"
-        os.environ.pop("KUKEON_SK4_SPLITK", None)
     print(line, flush=True)

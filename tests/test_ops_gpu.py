@@ -818,6 +818,58 @@ def test_linear_add_rmsnorm_fused(M):
                                atol=3e-2)
 
 
+def _fresh_skinny_workspace():
+    """Retire (never free: a captured graph may still point at it) the
+    cached split-K workspace, so the next dispatch allocates the buffer
+    the plan sizes."""
+    ops._SKINNY_WS_RETIRED.extend(ops._SKINNY_WS.values())
+    ops._SKINNY_WS.clear()
+
+
+@pytest.mark.parametrize("M", [1, 17, 64])
+def test_linear_dispatch_v5_plan_sized_workspace(M):
+    """ops.linear on the down-projection shape: v5 through the Python
+    dispatch, writing its slabs into a workspace of exactly the size the
+    launcher's own plan reports."""
+    torch.manual_seed(13)
+    N, K = 4096, 14336
+    x = (torch.randn(M, K, dtype=torch.bfloat16, device=DEV) * 0.5)
+    w = (torch.randn(N, K, dtype=torch.bfloat16, device=DEV) * 0.05)
+    _fresh_skinny_workspace()
+    out = ops.linear(x, w)
+    ref = (x.float() @ w.float().T)
+    torch.testing.assert_close(out.float().cpu(), ref.cpu(), rtol=3e-2,
+                               atol=6e-2)
+    assert ops._SKINNY_WS[0].numel() == 64 * 4096 * 4
+
+
+@pytest.mark.parametrize("M", [1, 17, 64])
+def test_linear_add_rmsnorm_dispatch_v5_plan_sized_workspace(M):
+    """ops.linear_add_rmsnorm on the down-projection shape (v5 + fused
+    reduce/add/RMSNorm) vs the unfused reference chain, with the
+    plan-sized workspace."""
+    torch.manual_seed(7)
+    N, K = 4096, 14336
+    x = torch.randn(M, K, dtype=torch.bfloat16, device=DEV) * 0.3
+    w = torch.randn(N, K, dtype=torch.bfloat16, device=DEV) * 0.05
+    resid = torch.randn(M, N, dtype=torch.bfloat16, device=DEV)
+    nw = torch.rand(N, dtype=torch.bfloat16, device=DEV) + 0.5
+    eps = 1e-5
+    resid_ref = resid.clone()
+    _fresh_skinny_workspace()
+    normed = ops.linear_add_rmsnorm(x, w, resid, nw, eps)
+    # reference: fp32 gemm -> bf16 add -> rmsnorm
+    y = (x.float() @ w.float().T)
+    r2 = (resid_ref.float() + y).to(torch.bfloat16).float()
+    ref = (r2 * torch.rsqrt(r2.pow(2).mean(-1, keepdim=True) + eps) *
+           nw.float())
+    torch.testing.assert_close(normed.float().cpu(), ref.cpu(), rtol=4e-2,
+                               atol=6e-2)
+    torch.testing.assert_close(resid.float().cpu(), r2.cpu(), rtol=3e-2,
+                               atol=5e-2)
+    assert ops._SKINNY_WS[0].numel() == 64 * 4096 * 4
+
+
 def test_modelhub_server_gpu_streaming():
     """The serving stack end to end on the GPU: engine-loop thread with
     hipGraphs, unix-socket protocol, concurrent sessions, streaming."""
