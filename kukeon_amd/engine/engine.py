@@ -444,14 +444,10 @@ class LLMEngine:
         return self.Bmax
 
     def _decode_splits(self, bucket: int) -> int:
-        # target ~8x the 256 CUs in workgroups: the micro-bench
-        # (scripts/bench_paged_attn.py) shows 2048-4096 WGs runs 5-9%
-        # faster than the 512-WG minimum (imbalance absorption across
-        # the 8 XCDs), flat beyond
-        # target ~4096 split-units: the MFMA decode kernel runs B*Hk*S
+        # target ~4096 split slots: the decode kernel runs B*Hk*S
         # autonomous waves (4 per workgroup), and 4096 exactly fills the
-        # chip at its 4-waves/SIMD occupancy (multiple of 4 required —
-        # each workgroup's waves own consecutive split slots)
+        # chip at its 4-waves/SIMD occupancy. A multiple of 4 keeps every
+        # workgroup's 4 waves busy (each owns one of 4 consecutive slots).
         want = (16 * 256 + bucket * self.hk - 1) // (bucket * self.hk)
         return max(4, min(self.max_splits, ((want + 3) // 4) * 4))
 

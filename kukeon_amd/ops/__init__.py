@@ -80,6 +80,13 @@ def decode_advance(ids, pos, seq_lens, tokens, ring, counter) -> None:
 def paged_attention(out, q, k_cache, v_cache, block_table, seq_lens,
                     q_offset: int, num_splits: int, scale: float,
                     tmp_out, tmp_ml) -> None:
+    """Decode attention of one query token per row of `q` against the
+    paged KV cache, split `num_splits` (>= 1) ways along the context.
+
+    `tmp_out` / `tmp_ml` are float32 workspaces of at least
+    B*Hq*num_splits*128 and B*Hq*num_splits*2 elements. A row with
+    seq_len <= 0 leaves its `out` row untouched on the GPU (the CPU
+    reference zeroes it)."""
     _impl(q).paged_attention(out, q, k_cache, v_cache, block_table, seq_lens,
                              q_offset, num_splits, scale, tmp_out, tmp_ml)
 

@@ -24,6 +24,7 @@ SOURCES = [
     "rope_kv.hip",
     "paged_attn.hip",
     "prefill_attn.hip",
+    "mfma_probe.hip",
     "sampling.hip",
     "moe.hip",
     "moe_grouped.hip",

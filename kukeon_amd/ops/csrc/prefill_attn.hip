@@ -1,6 +1,4 @@
-// Varlen causal paged prefill attention (MFMA, bf16) for gfx950 — plus the
-// fragment-layout probe used by the GPU test suite to pin the
-// v_mfma_f32_32x32x16_bf16 operand maps this kernel relies on.
+// Varlen causal paged prefill attention (MFMA, bf16) for gfx950.
 //
 // Structure (MI355X-first; guide §Appendix B attention recipe adapted to a
 // paged varlen serving kernel):
@@ -11,114 +9,19 @@
 //     column -> online softmax is lane-local (+ one shfl_xor(32) exchange
 //     between the two half-wave row sets).
 //   - P -> bf16 via packed cvt (v_cvt_pk_bf16_f32) + permlane32_swap to
-//     rebuild k-contiguous MFMA A.. er B-fragments without an LDS bounce.
+//     rebuild k-contiguous MFMA B-fragments without an LDS bounce.
 //   - PV as O^T = V^T·P^T with V staged TRANSPOSED into LDS (ushort2
 //     interleave at stage time, slot-XOR swizzle), so the V fragment read is
 //     a single ds_read_b128.
 //   - K tile XOR-swizzled ((row&15)<<4) -> conflict-free ds_read_b128
 //     (guide G4: row-major D=128 tiles are a 16-way conflict otherwise).
 //
-// Assumed gfx950 fragment maps (validated by tests/test_ops_gpu.py):
-//   A[32x16k]: lane l -> row = l&31, k = 8*(l>>5) + j   (j = 0..7, bf16x8)
-//   B[16kx32]: lane l -> col = l&31, k = 8*(l>>5) + j
-//   C/D:       lane l -> col = l&31, row = (r&3) + 8*(r>>2) + 4*(l>>5)
-#include "common.h"
+// Both MFMAs are 32x32x16; attn_frag.h documents the lane maps.
+#include "attn_frag.h"
 #include <torch/extension.h>
 #include <c10/hip/HIPStream.h>
 
 namespace kukeon {
-
-typedef __attribute__((__vector_size__(8 * sizeof(short)))) short bf16x8_t;
-typedef __attribute__((__vector_size__(16 * sizeof(float)))) float f32x16_t;
-
-struct uint4_t { unsigned int x[4]; };
-DEV_INLINE bf16x8_t as_frag(unsigned int w0, unsigned int w1, unsigned int w2,
-                            unsigned int w3) {
-  uint4_t v{{w0, w1, w2, w3}};
-  return __builtin_bit_cast(bf16x8_t, v);
-}
-
-// ---------- layout probe: C[32,32] = A[32,16] @ B[16,32] ----------
-__global__ void mfma_probe_kernel(float* __restrict__ c,
-                                  const unsigned short* __restrict__ a,
-                                  const unsigned short* __restrict__ b) {
-  const int lane = threadIdx.x & 63;
-  const int hi = lane >> 5;
-  const int rc = lane & 31;
-  unsigned int areg[4], breg[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int k0 = 8 * hi + 2 * i;
-    areg[i] = (unsigned)a[rc * 16 + k0] | ((unsigned)a[rc * 16 + k0 + 1] << 16);
-    breg[i] = (unsigned)b[k0 * 32 + rc] | ((unsigned)b[(k0 + 1) * 32 + rc] << 16);
-  }
-  f32x16_t acc = {};
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-      as_frag(areg[0], areg[1], areg[2], areg[3]),
-      as_frag(breg[0], breg[1], breg[2], breg[3]), acc, 0, 0, 0);
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int row = (r & 3) + 8 * (r >> 2) + 4 * hi;
-    c[row * 32 + rc] = acc[r];
-  }
-}
-
-__global__ void mfma_probe16_kernel(float* __restrict__ c,
-                                    const unsigned short* __restrict__ a,
-                                    const unsigned short* __restrict__ b) {
-  typedef __attribute__((__vector_size__(4 * sizeof(float)))) float f32x4_t;
-  const int lane = threadIdx.x & 63;
-  const int g = lane >> 4;     // k group
-  const int rc = lane & 15;
-  unsigned int areg[4], breg[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int k0 = 8 * g + 2 * i;
-    areg[i] = (unsigned)a[rc * 32 + k0] | ((unsigned)a[rc * 32 + k0 + 1] << 16);
-    breg[i] = (unsigned)b[k0 * 16 + rc] | ((unsigned)b[(k0 + 1) * 16 + rc] << 16);
-  }
-  f32x4_t acc = {};
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-      as_frag(areg[0], areg[1], areg[2], areg[3]),
-      as_frag(breg[0], breg[1], breg[2], breg[3]), acc, 0, 0, 0);
-#pragma unroll
-  for (int r = 0; r < 4; ++r) c[(4 * g + r) * 16 + rc] = acc[r];
-}
-
-void mfma_probe16(torch::Tensor out, torch::Tensor a, torch::Tensor b) {
-  TORCH_CHECK(a.sizes() == torch::IntArrayRef({16, 32}));
-  TORCH_CHECK(b.sizes() == torch::IntArrayRef({32, 16}));
-  TORCH_CHECK(out.sizes() == torch::IntArrayRef({16, 16}));
-  auto stream = c10::hip::getCurrentHIPStream().stream();
-  mfma_probe16_kernel<<<1, 64, 0, stream>>>(
-      out.data_ptr<float>(),
-      reinterpret_cast<const unsigned short*>(a.data_ptr()),
-      reinterpret_cast<const unsigned short*>(b.data_ptr()));
-  HIP_CHECK_KERNEL();
-}
-
-void mfma_probe(torch::Tensor out, torch::Tensor a, torch::Tensor b) {
-  TORCH_CHECK(a.sizes() == torch::IntArrayRef({32, 16}));
-  TORCH_CHECK(b.sizes() == torch::IntArrayRef({16, 32}));
-  TORCH_CHECK(out.sizes() == torch::IntArrayRef({32, 32}));
-  TORCH_CHECK(a.scalar_type() == torch::kBFloat16 && a.is_contiguous());
-  TORCH_CHECK(out.scalar_type() == torch::kFloat32);
-  auto stream = c10::hip::getCurrentHIPStream().stream();
-  mfma_probe_kernel<<<1, 64, 0, stream>>>(
-      out.data_ptr<float>(),
-      reinterpret_cast<const unsigned short*>(a.data_ptr()),
-      reinterpret_cast<const unsigned short*>(b.data_ptr()));
-  HIP_CHECK_KERNEL();
-}
-
-// ---------- helpers ----------
-DEV_INLINE unsigned int cvt_pk_bf16(float lo, float hi) {
-  // lowers to v_cvt_pk_bf16_f32 (don't hand-write the asm: guide T12)
-  __hip_bfloat162 h = __float22bfloat162_rn(float2{lo, hi});
-  unsigned int r;
-  __builtin_memcpy(&r, &h, 4);
-  return r;
-}
 
 // ---------- the kernel ----------
 // D=128, QBLK=32 rows per workgroup, KV tile = 32 tokens (2 cache blocks).
@@ -187,6 +90,8 @@ __global__ __launch_bounds__(256, 1) void prefill_attn_kernel(
     // ---- cooperative stage ----
     {
       __syncthreads();  // protect previous tile's readers
+      const auto* kc = reinterpret_cast<const kv_elem_t<FP8>*>(k_cache);
+      const auto* vc = reinterpret_cast<const kv_elem_t<FP8>*>(v_cache);
       // K: thread covers (tok = tid/8, d0 = (tid%8)*16), 2 x 16B
       const int tok = threadIdx.x >> 3;
       const int d0 = (threadIdx.x & 7) * 16;
@@ -197,21 +102,12 @@ __global__ __launch_bounds__(256, 1) void prefill_attn_kernel(
       const int swz = (tok & 15) << 4;
 #pragma unroll
       for (int c = 0; c < 2; ++c) {
-        uint4 v;
-        if (FP8) {
-          v = fp8x8_to_bf16x8(*reinterpret_cast<const uint2*>(
-              reinterpret_cast<const unsigned char*>(k_cache) + koff + d0 +
-              c * 8));
-        } else {
-          v = *reinterpret_cast<const uint4*>(
-              reinterpret_cast<const unsigned short*>(k_cache) + koff + d0 +
-              c * 8);
-        }
         const int byte = tok * 256 + (((d0 + c * 8) * 2) ^ swz);
-        *reinterpret_cast<uint4*>(
-            reinterpret_cast<char*>(kbuf) + byte) = v;
+        *reinterpret_cast<uint4*>(reinterpret_cast<char*>(kbuf) + byte) =
+            load_kv8(kc + koff + d0 + c * 8);
       }
-      // V: thread covers (kv pair = tid/16, d0 = (tid%16)*8), transpose
+      // V: thread covers (kv pair = tid/16, d0 = (tid%16)*8), transposed
+      // into the V^T image (attn_frag.h; pitch 64 B, swizzle << 4)
       const int kp = threadIdx.x >> 4;          // 0..15 -> kv = 2*kp
       const int vd0 = (threadIdx.x & 15) * 8;
       const int vpos0 = kvbase + 2 * kp;
@@ -224,20 +120,8 @@ __global__ __launch_bounds__(256, 1) void prefill_attn_kernel(
       const long voff1 =
           (((long)block_table[(long)s * max_blocks + vb1] * Hk + hk) * BS +
            (vpos1 % BS)) * D;
-      uint4 r0, r1;
-      if (FP8) {
-        const unsigned char* v8 =
-            reinterpret_cast<const unsigned char*>(v_cache);
-        r0 = fp8x8_to_bf16x8(
-            *reinterpret_cast<const uint2*>(v8 + voff0 + vd0));
-        r1 = fp8x8_to_bf16x8(
-            *reinterpret_cast<const uint2*>(v8 + voff1 + vd0));
-      } else {
-        const unsigned short* v16 =
-            reinterpret_cast<const unsigned short*>(v_cache);
-        r0 = *reinterpret_cast<const uint4*>(v16 + voff0 + vd0);
-        r1 = *reinterpret_cast<const uint4*>(v16 + voff1 + vd0);
-      }
+      uint4 r0 = load_kv8(vc + voff0 + vd0);
+      uint4 r1 = load_kv8(vc + voff1 + vd0);
       // zero V rows past ctx: a 0*NaN in the PV mfma would poison O
       if (vpos0 >= ctx) r0 = uint4{0, 0, 0, 0};
       if (vpos1 >= ctx) r1 = uint4{0, 0, 0, 0};
@@ -303,7 +187,7 @@ __global__ __launch_bounds__(256, 1) void prefill_attn_kernel(
     // ---- P -> bf16 B-fragments via cvt_pk + permlane32_swap ----
     unsigned int cp[8];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) cp[j] = cvt_pk_bf16(p[2 * j], p[2 * j + 1]);
+    for (int j = 0; j < 8; ++j) cp[j] = cvtpk_bf16(p[2 * j], p[2 * j + 1]);
     unsigned int pb[2][4];  // [kv chunk][4 dwords = 8 bf16, k-contiguous]
 #pragma unroll
     for (int c = 0; c < 2; ++c) {
@@ -343,9 +227,9 @@ __global__ __launch_bounds__(256, 1) void prefill_attn_kernel(
 #pragma unroll
     for (int quad = 0; quad < 4; ++quad) {
       const int d = db * 32 + quad * 8 + 4 * hi;
-      const unsigned int w0 = cvt_pk_bf16(oacc[db][quad * 4 + 0] * inv,
+      const unsigned int w0 = cvtpk_bf16(oacc[db][quad * 4 + 0] * inv,
                                           oacc[db][quad * 4 + 1] * inv);
-      const unsigned int w1 = cvt_pk_bf16(oacc[db][quad * 4 + 2] * inv,
+      const unsigned int w1 = cvtpk_bf16(oacc[db][quad * 4 + 2] * inv,
                                           oacc[db][quad * 4 + 3] * inv);
       *reinterpret_cast<uint2*>(orow + d) = uint2{w0, w1};
     }

@@ -14,8 +14,9 @@ def case(ctx, Hq, Hk, tag):
     sl = torch.tensor([ctx], dtype=torch.int32, device=DEV)
     q = torch.randn(1, Hq * D, dtype=torch.bfloat16, device=DEV)
     out = torch.empty(1, Hq * D, dtype=torch.bfloat16, device=DEV)
-    t1 = torch.zeros(1, dtype=torch.float32, device=DEV)
-    ops.paged_attention(out, q, kc, vc, bt, sl, 0, 1, 1.0, t1, t1)
+    tmp_out = torch.zeros(1, Hq, 1, D, dtype=torch.float32, device=DEV)
+    tmp_ml = torch.zeros(1, Hq, 1, 2, dtype=torch.float32, device=DEV)
+    ops.paged_attention(out, q, kc, vc, bt, sl, 0, 1, 1.0, tmp_out, tmp_ml)
     ref = torch.empty(1, Hq * D, dtype=torch.bfloat16)
     reference.paged_attention(ref, q.cpu(), kc.cpu(), vc.cpu(), bt.cpu(), sl.cpu(), 0, 1, 1.0)
     o = out.cpu().float().view(Hq, D)
