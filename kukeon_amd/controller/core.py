@@ -1606,7 +1606,8 @@ class Controller:
     def provision_modelhub_cell(self, model: str = "llama-3-8b",
                                 gpus: int = 1, socket_path: str = "",
                                 extra_args: Optional[List[str]] = None,
-                                start: bool = True) -> api.CellDoc:
+                                start: bool = True,
+                                weight_dtype: str = "") -> api.CellDoc:
         """Provision the inference server as a system-realm cell (the same
         pattern the reference uses for kukeond itself)."""
         import sys as _sys
@@ -1617,6 +1618,8 @@ class Controller:
         sock = socket_path or str(self.run_path / "modelhub.sock")
         args = ["-m", "kukeon_amd.serve.server", "--model", model,
                 "--socket", sock] + list(extra_args or [])
+        if weight_dtype:
+            args += ["--weight-dtype", weight_dtype]
         doc = api.CellDoc(
             metadata=api.Metadata(name="modelhub"),
             spec=api.CellSpec(

@@ -80,8 +80,35 @@ def _init_weight(shape, device, std=0.02, seed=None):
     return nn.Parameter(w, requires_grad=False)
 
 
+WEIGHT_DTYPES = ("bf16", "fp8")
+
+
+def resolve_weight_dtype(weight_dtype: Optional[str]) -> str:
+    """The weight storage a model is built with: the argument when given,
+    else KUKEON_WEIGHT_DTYPE, else bf16."""
+    if weight_dtype is None:
+        import os
+        weight_dtype = os.environ.get("KUKEON_WEIGHT_DTYPE") or "bf16"
+    if weight_dtype not in WEIGHT_DTYPES:
+        raise ValueError(f"weight_dtype must be one of {WEIGHT_DTYPES}, "
+                         f"got {weight_dtype!r}")
+    return weight_dtype
+
+
+def _make_weight(shape, device, weight_dtype: str):
+    """A GEMM weight: the bf16 Parameter, or with fp8 its quantisation.
+    The bf16 tensor is drawn first and dropped right after, so the RNG
+    stream is the bf16 model's and peak memory is the fp8 model plus one
+    bf16 weight."""
+    w = _init_weight(shape, device)
+    if weight_dtype == "fp8":
+        return ops.quantize_weight(w.data)
+    return w
+
+
 class LlamaAttention(nn.Module):
-    def __init__(self, cfg: ModelConfig, layer_idx: int, device):
+    def __init__(self, cfg: ModelConfig, layer_idx: int, device,
+                 weight_dtype: str = "bf16"):
         super().__init__()
         tp = parallel.tp_size()
         assert cfg.num_q_heads % tp == 0 and cfg.num_kv_heads % tp == 0, (
@@ -92,8 +119,10 @@ class LlamaAttention(nn.Module):
         self.d = cfg.head_dim
         self.scale = cfg.head_dim ** -0.5
         qkv_out = (self.hq + 2 * self.hk) * self.d
-        self.qkv_w = _init_weight((qkv_out, cfg.hidden_size), device)
-        self.o_w = _init_weight((cfg.hidden_size, self.hq * self.d), device)
+        self.qkv_w = _make_weight((qkv_out, cfg.hidden_size), device,
+                                  weight_dtype)
+        self.o_w = _make_weight((cfg.hidden_size, self.hq * self.d), device,
+                                weight_dtype)
 
     def forward(self, x: torch.Tensor, cos_sin: torch.Tensor,
                 kc: torch.Tensor, vc: torch.Tensor, meta: AttnMeta):
@@ -139,13 +168,15 @@ class LlamaAttention(nn.Module):
 
 
 class LlamaMLP(nn.Module):
-    def __init__(self, cfg: ModelConfig, device):
+    def __init__(self, cfg: ModelConfig, device, weight_dtype: str = "bf16"):
         super().__init__()
         tp = parallel.tp_size()
         assert cfg.intermediate_size % tp == 0
         self.inter = cfg.intermediate_size // tp
-        self.gate_up_w = _init_weight((2 * self.inter, cfg.hidden_size), device)
-        self.down_w = _init_weight((cfg.hidden_size, self.inter), device)
+        self.gate_up_w = _make_weight((2 * self.inter, cfg.hidden_size),
+                                      device, weight_dtype)
+        self.down_w = _make_weight((cfg.hidden_size, self.inter), device,
+                                   weight_dtype)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         gu = ops.linear(x, self.gate_up_w)
@@ -156,7 +187,8 @@ class LlamaMLP(nn.Module):
 
 
 class LlamaLayer(nn.Module):
-    def __init__(self, cfg: ModelConfig, layer_idx: int, device):
+    def __init__(self, cfg: ModelConfig, layer_idx: int, device,
+                 weight_dtype: str = "bf16"):
         super().__init__()
         self.input_norm = nn.Parameter(
             torch.ones(cfg.hidden_size, dtype=torch.bfloat16, device=device),
@@ -164,8 +196,8 @@ class LlamaLayer(nn.Module):
         self.post_norm = nn.Parameter(
             torch.ones(cfg.hidden_size, dtype=torch.bfloat16, device=device),
             requires_grad=False)
-        self.attn = LlamaAttention(cfg, layer_idx, device)
-        self.mlp = LlamaMLP(cfg, device)
+        self.attn = LlamaAttention(cfg, layer_idx, device, weight_dtype)
+        self.mlp = LlamaMLP(cfg, device, weight_dtype)
         self.eps = cfg.rms_eps
 
     def forward(self, x, residual, cos_sin, kc, vc, meta):
@@ -224,23 +256,46 @@ class LlamaLayer(nn.Module):
 
 class LlamaModel(nn.Module):
     """Random-init Llama decoder for the serving engine (bench contract:
-    synthetic data / random weights — no checkpoints in this environment)."""
+    synthetic data / random weights — no checkpoints in this environment).
 
-    def __init__(self, cfg: ModelConfig, device="cuda"):
+    weight_dtype "fp8" stores qkv/o/gate_up/down/lm_head as ops.Fp8Weight
+    (e4m3 bytes + per-output-channel scales, quantised per TP shard); the
+    embedding, the norms and the RoPE table stay as they are. None reads
+    KUKEON_WEIGHT_DTYPE (default bf16)."""
+
+    def __init__(self, cfg: ModelConfig, device="cuda",
+                 weight_dtype: Optional[str] = None):
         super().__init__()
         self.cfg = cfg
+        self.weight_dtype = resolve_weight_dtype(weight_dtype)
         self.device_ = torch.device(device)
         torch.manual_seed(42)
         self.embed = _init_weight((cfg.vocab_size, cfg.hidden_size),
                                   self.device_)
         self.layers = nn.ModuleList(
-            [LlamaLayer(cfg, i, self.device_) for i in range(cfg.num_layers)])
+            [LlamaLayer(cfg, i, self.device_, self.weight_dtype)
+             for i in range(cfg.num_layers)])
         self.final_norm = nn.Parameter(
             torch.ones(cfg.hidden_size, dtype=torch.bfloat16,
                        device=self.device_), requires_grad=False)
-        self.lm_head = _init_weight((cfg.vocab_size, cfg.hidden_size),
-                                    self.device_)
+        self.lm_head = _make_weight((cfg.vocab_size, cfg.hidden_size),
+                                    self.device_, self.weight_dtype)
         self.cos_sin = self._build_rope_table().to(self.device_)
+
+    def gemm_weights(self):
+        """(name, weight) of every GEMM weight the weight dtype governs."""
+        for i, layer in enumerate(self.layers):
+            yield f"layers.{i}.qkv_w", layer.attn.qkv_w
+            yield f"layers.{i}.o_w", layer.attn.o_w
+            yield f"layers.{i}.gate_up_w", layer.mlp.gate_up_w
+            yield f"layers.{i}.down_w", layer.mlp.down_w
+        yield "lm_head", self.lm_head
+
+    def resident_weight_bytes(self) -> int:
+        """Bytes of device memory the model's weights hold."""
+        n = sum(p.numel() * p.element_size() for p in self.parameters())
+        return n + sum(w.nbytes for _, w in self.gemm_weights()
+                       if isinstance(w, ops.Fp8Weight))
 
     def _build_rope_table(self) -> torch.Tensor:
         cfg = self.cfg

@@ -286,9 +286,16 @@ class MixtralLayer(nn.Module):
 
 
 class MixtralModel(nn.Module):
-    def __init__(self, cfg: ModelConfig, device="cuda"):
+    def __init__(self, cfg: ModelConfig, device="cuda", weight_dtype=None):
         super().__init__()
-        from kukeon_amd.models.llama import LlamaModel
+        from kukeon_amd.models.llama import LlamaModel, resolve_weight_dtype
+        self.weight_dtype = resolve_weight_dtype(weight_dtype)
+        if self.weight_dtype != "bf16":
+            # the expert weights run through bmm and the grouped GEMM,
+            # which read bf16 only; quantising them is separate work
+            raise ValueError(
+                "MixtralModel supports weight_dtype='bf16' only: fp8 "
+                "expert weights (bmm / grouped GEMM) are not implemented")
         self.cfg = cfg
         self.device_ = torch.device(device)
         torch.manual_seed(43)

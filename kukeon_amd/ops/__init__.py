@@ -190,9 +190,110 @@ def _skinny_workspace(device: torch.device, kind: str, N: int,
     return ws
 
 
-def linear(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+class Fp8Weight:
+    """A weight-only-quantised [N, K] weight: `q` uint8 [N, K] holding OCP
+    e4m3fn bytes (the storage the fp8 KV cache uses) and `scale` f32 [N],
+    one per output channel; the weight it stands for is
+    float(q) * scale[:, None]. linear / linear_add_rmsnorm /
+    mlp_down_fused take one wherever they take a bf16 weight."""
+
+    __slots__ = ("q", "scale")
+
+    def __init__(self, q: torch.Tensor, scale: torch.Tensor):
+        assert q.dtype == torch.uint8 and q.dim() == 2
+        assert scale.dtype == torch.float32 and scale.shape == (q.shape[0],)
+        self.q = q
+        self.scale = scale
+
+    @property
+    def shape(self):
+        return tuple(self.q.shape)
+
+    @property
+    def device(self) -> torch.device:
+        return self.q.device
+
+    @property
+    def is_cuda(self) -> bool:
+        return self.q.is_cuda
+
+    @property
+    def nbytes(self) -> int:
+        return self.q.numel() + 4 * self.scale.numel()
+
+
+# bf16 scratch a wide-M (prefill, > 64 rows) linear dequantises an
+# Fp8Weight into, one per device, as large as the largest weight
+# quantised there; outgrown ones are pinned like the split-K workspaces
+_W8_SCRATCH = {}
+_W8_SCRATCH_RETIRED = []
+
+
+def _w8_scratch(device: torch.device, numel: int) -> torch.Tensor:
+    key = (device.index or 0)
+    buf = _W8_SCRATCH.get(key)
+    if buf is None or buf.numel() < numel:
+        # grown only outside graph capture: quantize_weight reserves the
+        # size of every weight when the model is built
+        if buf is not None:
+            _W8_SCRATCH_RETIRED.append(buf)
+        buf = torch.empty(numel, dtype=torch.bfloat16, device=device)
+        _W8_SCRATCH[key] = buf
+    return buf
+
+
+def quantize_weight(w: torch.Tensor) -> Fp8Weight:
+    """Quantise a bf16 [N, K] weight to fp8 with per-output-channel
+    scales (scale = amax / 448, round-to-nearest-even)."""
+    w = w.detach().contiguous()
+    N, K = w.shape
+    q = torch.empty(N, K, dtype=torch.uint8, device=w.device)
+    scale = torch.empty(N, dtype=torch.float32, device=w.device)
+    _impl(w).quantize_fp8_rows(q, scale, w)
+    if w.is_cuda:
+        _w8_scratch(w.device, N * K)
+    return Fp8Weight(q, scale)
+
+
+def dequantize_weight(fw: Fp8Weight, out: torch.Tensor = None) -> torch.Tensor:
+    """bf16(float(q) * scale) as [N, K]; into `out` when given."""
+    if out is None:
+        out = torch.empty(fw.shape, dtype=torch.bfloat16, device=fw.device)
+    _impl(fw.q).dequant_fp8_rows(out, fw.q, fw.scale)
+    return out
+
+
+def _w8_skinny(x: torch.Tensor, fw: Fp8Weight) -> bool:
+    """Whether the W8A16 decode kernel runs x @ fw: its shape contract."""
+    N, K = fw.shape
+    return (x.is_cuda and x.dim() == 2 and 1 <= x.shape[0] <= 64
+            and x.dtype == torch.bfloat16 and x.is_contiguous()
+            and N % 64 == 0 and K % 64 == 0)
+
+
+def _linear_w8(x: torch.Tensor, fw: Fp8Weight) -> torch.Tensor:
+    if not x.is_cuda:
+        return reference.linear_w8(x, fw.q, fw.scale)
+    N, K = fw.shape
+    if _w8_skinny(x, fw):
+        out = torch.empty(x.shape[0], N, dtype=x.dtype, device=x.device)
+        ws = _skinny_workspace(x.device, "w8", N, K)
+        _native().skinny_gemm_w8(out, x, fw.q, fw.scale, ws)
+        return out
+    # prefill, the 96-256 row decode buckets, odd shapes: widen to bf16
+    # scratch, then the library GEMM
+    w = _w8_scratch(x.device, N * K)[:N * K].view(N, K)
+    _native().dequant_fp8_rows(w, fw.q, fw.scale)
+    return torch.nn.functional.linear(x, w)
+
+
+def linear(x: torch.Tensor, w) -> torch.Tensor:
     """F.linear with the weight-streaming skinny-GEMM kernel on the decode
-    shapes where it measured faster than hipBLASLt; hipBLASLt otherwise."""
+    shapes where it measured faster than hipBLASLt; hipBLASLt otherwise.
+    An Fp8Weight runs the W8A16 kernel at up to 64 rows and dequantises
+    into scratch for the library above that."""
+    if isinstance(w, Fp8Weight):
+        return _linear_w8(x, w)
     kind = _skinny_kind(x, w, fused=False)
     if kind is None:
         return torch.nn.functional.linear(x, w)
@@ -216,7 +317,20 @@ def linear_add_rmsnorm(x: torch.Tensor, w: torch.Tensor,
     <1us of work. Mutates `residual` (+= x@w.T) and returns the normed
     activations, exactly like linear() followed by fused_add_rmsnorm().
     """
-    kind = _skinny_kind(x, w, fused=True)
+    if isinstance(w, Fp8Weight):
+        from kukeon_amd import parallel
+        N, K = w.shape
+        if (_w8_skinny(x, w) and parallel.tp_size() == 1
+                and N % 2048 == 0 and N <= 8192):
+            normed = torch.empty(x.shape[0], N, dtype=x.dtype,
+                                 device=x.device)
+            ws = _skinny_workspace(x.device, "w8", N, K)
+            _native().skinny_gemm_w8_fused_norm(normed, x, w.q, w.scale, ws,
+                                                residual, norm_weight, eps)
+            return normed
+        kind = None
+    else:
+        kind = _skinny_kind(x, w, fused=True)
     if kind is None:
         from kukeon_amd import parallel
         h = parallel.tp_all_reduce(linear(x, w))
@@ -247,7 +361,9 @@ def mlp_down_fused(gu: torch.Tensor, w: torch.Tensor,
     """
     rows = gu.shape[0]
     N, K = w.shape
-    if (_FUSE_SILU and gu.dim() == 2 and gu.shape[1] == 2 * K
+    # the silu-into-staging kernel reads bf16 W: an Fp8Weight goes unfused
+    if (_FUSE_SILU and not isinstance(w, Fp8Weight) and gu.dim() == 2
+            and gu.shape[1] == 2 * K
             and _skinny_kind(gu, w, fused=True) == "v5"):
         ws = _skinny_workspace(gu.device, "v5_fused", N, K)
         normed = torch.empty(rows, N, dtype=gu.dtype, device=gu.device)

@@ -29,6 +29,7 @@ SOURCES = [
     "moe.hip",
     "moe_grouped.hip",
     "skinny_gemm.hip",
+    "fp8_weight.hip",
     "bindings.cpp",
 ]
 

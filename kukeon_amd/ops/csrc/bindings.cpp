@@ -50,6 +50,15 @@ void skinny_gemm_fused_norm(torch::Tensor normed, torch::Tensor x,
                             torch::Tensor w, torch::Tensor ws,
                             torch::Tensor residual, torch::Tensor nw,
                             double eps);
+void skinny_gemm_w8(torch::Tensor out, torch::Tensor x, torch::Tensor q,
+                    torch::Tensor scale, torch::Tensor ws);
+void skinny_gemm_w8_fused_norm(torch::Tensor normed, torch::Tensor x,
+                               torch::Tensor q, torch::Tensor scale,
+                               torch::Tensor ws, torch::Tensor residual,
+                               torch::Tensor nw, double eps);
+void quantize_fp8_rows(torch::Tensor q, torch::Tensor scale, torch::Tensor w);
+void dequant_fp8_rows(torch::Tensor out, torch::Tensor q,
+                      torch::Tensor scale);
 void sample(torch::Tensor tokens, torch::Tensor logits, torch::Tensor temps,
             torch::Tensor top_k, torch::Tensor top_p, torch::Tensor seed,
             torch::Tensor workspace);
@@ -100,7 +109,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "weight-streaming decode GEMM (M<=64)");
   m.def("skinny_splitk", &kukeon::skinny_splitk,
         "split-K factor the skinny launcher of `kind` (v1, v2, v5, v5_fused, "
-        "v6) uses for [N, K]; host-only",
+        "v6, w8) uses for [N, K]; host-only",
         py::arg("kind"), py::arg("N"), py::arg("K"));
   m.def("glds_probe", &kukeon::glds_probe,
         "asm global_lds round-trip validator");
@@ -108,6 +117,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "skinny5 + fused split-K reduce + residual add + RMSNorm");
   m.def("skinny_gemm_fused_norm", &kukeon::skinny_gemm_fused_norm,
         "skinny GEMM + split-K reduce + residual add + RMSNorm");
+  m.def("skinny_gemm_w8", &kukeon::skinny_gemm_w8,
+        "W8A16 decode GEMM: (x @ fp8(q)^T) * scale, M<=64");
+  m.def("skinny_gemm_w8_fused_norm", &kukeon::skinny_gemm_w8_fused_norm,
+        "W8A16 decode GEMM + split-K reduce + residual add + RMSNorm");
+  m.def("quantize_fp8_rows", &kukeon::quantize_fp8_rows,
+        "bf16 [N,K] -> e4m3fn bytes + per-row f32 scale (amax/448)");
+  m.def("dequant_fp8_rows", &kukeon::dequant_fp8_rows,
+        "out = bf16(fp8(q) * scale[n])");
   m.def("sample", &kukeon::sample, "top-k/top-p/temperature sampling");
   m.def("decode_advance", &kukeon::decode_advance,
         "on-device decode cursor advance (self-advancing graph)");

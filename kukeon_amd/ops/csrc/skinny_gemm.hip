@@ -20,8 +20,9 @@
 //
 // Layout of this file: the kernels first — v1 (above; o-projection), the
 // two split-K epilogues, v2 (G-tile walk, hand-counted waits), v5
-// (full-line W stream; down-projection) and v6 (barrier-free); v2, v6
-// and v5's silu path are tested negative results. The host side sits at
+// (full-line W stream; down-projection), v6 (barrier-free) and W8A16
+// (fp8 weight bytes, per-row scales); v2, v6 and v5's silu path are
+// tested negative results. The host side sits at
 // the end: one split-K plan (skinny_plan, exported to Python as
 // skinny_splitk so the workspace is sized by the same formula), one
 // launcher skeleton (run_reduce / run_reduce_add_rmsnorm), and one short
@@ -970,6 +971,187 @@ __global__ __launch_bounds__(256) void skinny6_kernel(
 }
 
 // ===========================================================================
+// W8A16: out[M,N] = (x[M,K] @ float(q[N,K])^T) * scale[N], q = OCP e4m3fn
+// bytes with one f32 scale per output row (ops.Fp8Weight).
+//
+// v1's staging with a 1-byte W stream. e4m3 -> bf16 is exact, so the
+// bytes are widened in registers and feed the same bf16 MFMA into the same
+// f32 accumulators; x is not quantised. A lane's 16-B load is 16 k values
+// of one row, spent on two MFMAs whose x fragments sit 8 k apart in the
+// xswz image (the sum over k has no order, so A and B only have to agree
+// on which k a lane holds). One load instruction covers 16 rows x 64 B and
+// a slice's batch of 4 covers two whole 128-B lines per row. scale[n]
+// multiplies the f32 accumulator on the way out, on the direct store and
+// on the slab store alike (linear per column), so both split-K epilogues
+// are shared unchanged. Requires N%64 == 0 and K%64 == 0.
+// ===========================================================================
+constexpr int W8_U = KSLICE / 64;  // 16-B W loads per lane per full slice
+
+template <int MT>
+DEV_INLINE void w8_consume(u32x4_t wv, const unsigned short* xb,
+                           f32x4_t (&acc)[MT], int kc0, int row16) {
+  const uint4 lo = fp8x8_to_bf16x8(uint2{wv[0], wv[1]});
+  const uint4 hi = fp8x8_to_bf16x8(uint2{wv[2], wv[3]});
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const bf16x8_t afrag = frag_of(h == 0 ? lo : hi);
+    const int kc = kc0 + 8 * h;
+#pragma unroll
+    for (int m = 0; m < MT; ++m) {
+      const int xr = m * 16 + row16;
+      const uint4 xv = *reinterpret_cast<const uint4*>(
+          reinterpret_cast<const char*>(xb) + xswz(xr, kc * 2));
+      acc[m] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+          afrag, frag_of(xv), acc[m], 0, 0, 0);
+    }
+  }
+}
+
+template <int MT, bool SPLIT>
+__global__ __launch_bounds__(256) void skinny_w8_kernel(
+    unsigned short* __restrict__ out,      // [M, N] bf16 (SPLIT=false)
+    float* __restrict__ ws,                // [splitk, M, N] f32 (SPLIT)
+    const unsigned short* __restrict__ x,  // [M, K] bf16
+    const unsigned char* __restrict__ q,   // [N, K] e4m3fn
+    const float* __restrict__ scale,       // [N]
+    int M, int N, long K) {
+  __shared__ __align__(16) unsigned short xbuf[2][64 * KSLICE];
+  const int wid = threadIdx.x / WAVE;
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int n0 = blockIdx.x * 64 + wid * 16;     // this wave's 16 N rows
+  const int row16 = lane & 15;                   // A row / B col
+  const int kgrp = lane >> 4;                    // 0..3 -> k = 16*kgrp + j
+  f32x4_t acc[MT];
+#pragma unroll
+  for (int m = 0; m < MT; ++m) acc[m] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+
+  // this block walks slices ks0 + i*kstride: `nfull` whole ones, then the
+  // short tail slice if it falls to this block (only K's last slice can
+  // be short)
+  const long kstride = (long)gridDim.y * KSLICE;
+  const long ks0 = (long)blockIdx.y * KSLICE;
+  if (ks0 >= K) return;  // never: the plan clamps splitk to the slices
+  const int nall = (int)((K - ks0 + kstride - 1) / kstride);
+  const bool has_tail = ks0 + (long)(nall - 1) * kstride + KSLICE > K;
+  const int nfull = nall - (has_tail ? 1 : 0);
+  const unsigned char* wrow = q + (long)(n0 + row16) * K + ks0 + 16 * kgrp;
+
+  // Three W register sets rotate so that two slices of W stay in flight
+  // while a third is consumed (a drained stream pays the whole laden
+  // memory latency per slice; measured 2.1 us a slice on the down shape).
+  // Issue order in slice i, after its barrier: the staging DMAs of slice
+  // i+1, then the W loads of slice i+2. At the top of slice i the VM
+  // queue therefore holds W(i), DMA(i), W(i+1), oldest first, and the
+  // one explicit wait leaves exactly the W(i+1) loads in flight: every
+  // DMA is older than all the plain loads the wait counts, v1's ordering
+  // (vmcnt class-ordering, profiles/r02_progress.md item 1).
+  u32x4_t wa[3][W8_U];
+  auto issue = [&](u32x4_t (&w)[W8_U], int i) {
+#pragma unroll
+    for (int u = 0; u < W8_U; ++u)
+      w[u] = nt_load16(wrow + (long)i * kstride + u * 64);
+  };
+  auto stage = [&](int i) {
+    const long ks = ks0 + (long)i * kstride;
+    glds_stage_x(xbuf[i & 1], x, K, ks, (int)min((long)KSLICE, K - ks), M,
+                 wid, lane);
+  };
+  // one whole slice: AHEAD says the W of slice i+1 is in flight behind
+  // this one's (the explicit wait leaves it there), ISSUE sends slice
+  // i+2's W into `nxt2`. Both are compile-time so that the steady loop
+  // has no branch around a load: hipcc's own counted waits then stay
+  // exact (a conditional issue made it drain to vmcnt(0) every slice).
+  auto slice = [&](auto ahead, auto do_issue, u32x4_t (&cur)[W8_U],
+                   u32x4_t (&nxt2)[W8_U], int i) {
+    asm volatile("s_waitcnt vmcnt(%c0)" ::"i"(decltype(ahead)::value ? W8_U
+                                                                      : 0)
+                 : "memory");
+    __syncthreads();
+    // hipcc cannot count the DMAs: make it place its own wait for this
+    // slice's W here, where its count is exact, not after the issues
+    // below, where it would also wait out the DMAs
+#pragma unroll
+    for (int u = 0; u < W8_U; ++u) asm volatile("" : "+v"(cur[u]));
+    // safe without a second barrier: every wave finished reading the
+    // other x buffer (slice i-1) before it crossed this slice's barrier
+    if (i + 1 < nall) stage(i + 1);
+    if constexpr (decltype(do_issue)::value) issue(nxt2, i + 2);
+#pragma unroll
+    for (int u = 0; u < W8_U; ++u)
+      w8_consume<MT>(cur[u], xbuf[i & 1], acc, u * 64 + 16 * kgrp, row16);
+  };
+  constexpr std::true_type yes{};
+  constexpr std::false_type no{};
+  // the last two whole slices: nothing left to issue
+  auto last2 = [&](u32x4_t (&a)[W8_U], u32x4_t (&b)[W8_U], int i) {
+    slice(yes, no, a, a, i);
+    slice(no, no, b, b, i + 1);
+  };
+
+  stage(0);
+  if (nfull >= 2) {
+    issue(wa[0], 0);
+    issue(wa[1], 1);
+    // whole turns of the three sets in the loop, so that each set is one
+    // fixed group of registers all the way round (an exit in mid-turn
+    // made hipcc rotate the sets with copies, and wait for them)
+    const int nsteady = nfull - 2;  // slices with a slice i+2 to issue
+    int i = 0;
+    for (; i + 3 <= nsteady; i += 3) {
+      slice(yes, yes, wa[0], wa[2], i);
+      slice(yes, yes, wa[1], wa[0], i + 1);
+      slice(yes, yes, wa[2], wa[1], i + 2);
+    }
+    if (nsteady - i == 0) {
+      last2(wa[0], wa[1], i);
+    } else if (nsteady - i == 1) {
+      slice(yes, yes, wa[0], wa[2], i);
+      last2(wa[1], wa[2], i + 1);
+    } else {
+      slice(yes, yes, wa[0], wa[2], i);
+      slice(yes, yes, wa[1], wa[0], i + 1);
+      last2(wa[2], wa[0], i + 2);
+    }
+  } else if (nfull == 1) {
+    issue(wa[0], 0);
+    slice(no, no, wa[0], wa[0], 0);
+  }
+  if (has_tail) {
+    // klen in {64, 128, 192}: one 64-k chunk at a time, nothing else in
+    // flight (its x was staged during the last whole slice, or above)
+    const long ks = ks0 + (long)nfull * kstride;
+    const int klen = (int)(K - ks);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    for (int kc0 = 0; kc0 < klen; kc0 += 64)
+      w8_consume<MT>(nt_load16(wrow + (long)nfull * kstride + kc0),
+                     xbuf[nfull & 1], acc, kc0 + 16 * kgrp, row16);
+  }
+
+  // C layout: lane -> M index = lane&15, N index = n0 + 4*(lane>>4) + r
+  const int ncol = n0 + 4 * kgrp;
+  float sc[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) sc[r] = scale[ncol + r];
+  float* slab = SPLIT ? ws + (long)blockIdx.y * M * N : nullptr;
+#pragma unroll
+  for (int m = 0; m < MT; ++m) {
+    const int mrow = m * 16 + row16;
+    if (mrow >= M) continue;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const long off = (long)mrow * N + ncol + r;
+      const float v = acc[m][r] * sc[r];
+      if (SPLIT) {
+        slab[off] = v;
+      } else {
+        out[off] = f2us(v);
+      }
+    }
+  }
+}
+
+// ===========================================================================
 // Host side. Every variant is the same algorithm: split K over ~256 blocks,
 // run the GEMM kernel straight to bf16 (splitk == 1) or into splitk f32
 // slabs, then one of two epilogues. A variant differs only in its plan
@@ -1037,6 +1219,9 @@ static SkinnyPlan plan_v5(int M, int N, long K, int tiles, int KS) {
 static SkinnyPlan plan_v6(int M, int N, long K, int KS) {
   return skinny_plan(M, N, K, 128, KS, 256, "KUKEON_SK6_SPLITK");
 }
+static SkinnyPlan plan_w8(int M, int N, long K) {
+  return skinny_plan(M, N, K, 64, KSLICE, 512, "KUKEON_W8_SPLITK");
+}
 
 // The split-K factor a launcher will use, for sizing its workspace
 // (64 * N * splitk floats cover every M). Host-only.
@@ -1049,6 +1234,7 @@ int64_t skinny_splitk(const std::string& kind, int64_t N, int64_t K) {
   if (kind == "v5_fused") return plan_v5(1, n, K, sk5_tiles(), 128).splitk;
   if (kind == "v6")
     return plan_v6(1, n, K, ks_from_env("KUKEON_SK6_KS")).splitk;
+  if (kind == "w8") return plan_w8(1, n, K).splitk;
   TORCH_CHECK(false, "skinny_splitk: unknown kind ", kind);
 }
 
@@ -1076,22 +1262,34 @@ static float* slab_ptr(const SkinnyPlan& p, torch::Tensor& ws) {
   return ws.data_ptr<float>();
 }
 
-// Plain epilogue: `direct` writes bf16 itself at splitk == 1; otherwise
-// `split` fills the slabs and the reduce pass casts their sum to bf16.
-static void run_reduce(const SkinnyPlan& p, SkinnyKernel direct,
-                       SkinnyKernel split, torch::Tensor& out,
-                       const torch::Tensor& x, const torch::Tensor& w,
-                       torch::Tensor& ws) {
+// What a launcher hands the two epilogues: launch(split, out, ws, grid,
+// stream) starts the variant's GEMM kernel, the bf16-direct one or the
+// slab one. bf16_gemm() is that for every variant whose kernel has the
+// SkinnyKernel signature.
+static auto bf16_gemm(const SkinnyPlan& p, SkinnyKernel direct,
+                      SkinnyKernel split, const torch::Tensor& x,
+                      const torch::Tensor& w) {
+  return [=, &p](bool is_split, unsigned short* out, float* ws, dim3 grid,
+                 hipStream_t stream) {
+    (is_split ? split : direct)<<<grid, 256, 0, stream>>>(
+        out, ws, us_ptr(x), us_ptr(w), p.M, p.N, p.K);
+  };
+}
+
+// Plain epilogue: the direct kernel writes bf16 itself at splitk == 1;
+// otherwise the split kernel fills the slabs and the reduce pass casts
+// their sum to bf16.
+template <class Launch>
+static void run_reduce(const SkinnyPlan& p, Launch&& launch,
+                       torch::Tensor& out, torch::Tensor& ws) {
   auto stream = c10::hip::getCurrentHIPStream().stream();
   const dim3 grid(p.ngroups, p.splitk);
   if (p.splitk == 1) {
-    direct<<<grid, 256, 0, stream>>>(us_ptr(out), nullptr, us_ptr(x),
-                                     us_ptr(w), p.M, p.N, p.K);
+    launch(false, us_ptr(out), nullptr, grid, stream);
   } else {
     float* wsp = slab_ptr(p, ws);
     const long total = (long)p.M * p.N;
-    split<<<grid, 256, 0, stream>>>(nullptr, wsp, us_ptr(x), us_ptr(w), p.M,
-                                    p.N, p.K);
+    launch(true, nullptr, wsp, grid, stream);
     skinny_reduce_kernel<<<dim3((unsigned)((total / 8 + 255) / 256)), 256, 0,
                            stream>>>(us_ptr(out), wsp, total, p.splitk);
   }
@@ -1100,16 +1298,14 @@ static void run_reduce(const SkinnyPlan& p, SkinnyKernel direct,
 
 // Fused epilogue: always the slab kernel (also at splitk == 1), then
 // split-K reduce + residual add + RMSNorm in one kernel.
-static void run_reduce_add_rmsnorm(const SkinnyPlan& p, SkinnyKernel split,
-                                   torch::Tensor& normed,
-                                   const torch::Tensor& x,
-                                   const torch::Tensor& w, torch::Tensor& ws,
+template <class Launch>
+static void run_reduce_add_rmsnorm(const SkinnyPlan& p, Launch&& launch,
+                                   torch::Tensor& normed, torch::Tensor& ws,
                                    torch::Tensor& residual,
                                    const torch::Tensor& nw, double eps) {
   auto stream = c10::hip::getCurrentHIPStream().stream();
   float* wsp = slab_ptr(p, ws);
-  split<<<dim3(p.ngroups, p.splitk), 256, 0, stream>>>(
-      nullptr, wsp, us_ptr(x), us_ptr(w), p.M, p.N, p.K);
+  launch(true, nullptr, wsp, dim3(p.ngroups, p.splitk), stream);
   HIP_CHECK_KERNEL();
   skinny_reduce_add_rmsnorm_kernel<<<dim3((unsigned)p.M), 256, 0, stream>>>(
       us_ptr(normed), us_ptr(residual), wsp, us_ptr(nw), p.N,
@@ -1154,7 +1350,7 @@ void skinny_gemm(torch::Tensor out, torch::Tensor x, torch::Tensor w,
     direct = skinny_gemm_kernel<MT, false>;
     split = skinny_gemm_kernel<MT, true>;
   });
-  run_reduce(p, direct, split, out, x, w, ws);
+  run_reduce(p, bf16_gemm(p, direct, split, x, w), out, ws);
 }
 
 void skinny_gemm_fused_norm(torch::Tensor normed, torch::Tensor x,
@@ -1167,7 +1363,8 @@ void skinny_gemm_fused_norm(torch::Tensor normed, torch::Tensor x,
   with_mt(p.MT, [&](auto mt) {
     split = skinny_gemm_kernel<decltype(mt)::value, true>;
   });
-  run_reduce_add_rmsnorm(p, split, normed, x, w, ws, residual, nw, eps);
+  run_reduce_add_rmsnorm(p, bf16_gemm(p, nullptr, split, x, w), normed, ws,
+                         residual, nw, eps);
 }
 
 void skinny_gemm2(torch::Tensor out, torch::Tensor x, torch::Tensor w,
@@ -1180,7 +1377,7 @@ void skinny_gemm2(torch::Tensor out, torch::Tensor x, torch::Tensor w,
     direct = skinny2_kernel<MT, false>;
     split = skinny2_kernel<MT, true>;
   });
-  run_reduce(p, direct, split, out, x, w, ws);
+  run_reduce(p, bf16_gemm(p, direct, split, x, w), out, ws);
 }
 
 void skinny_gemm5(torch::Tensor out, torch::Tensor x, torch::Tensor w,
@@ -1200,7 +1397,7 @@ void skinny_gemm5(torch::Tensor out, torch::Tensor x, torch::Tensor w,
       split = sk5_kernel<MT, true, 256, false>(tiles);
     }
   });
-  run_reduce(p, direct, split, out, x, w, ws);
+  run_reduce(p, bf16_gemm(p, direct, split, x, w), out, ws);
 }
 
 // skinny5 + the split-K reduce fused with residual add + RMSNorm: the
@@ -1217,7 +1414,8 @@ void skinny_gemm5_fused_norm(torch::Tensor normed, torch::Tensor x,
   with_mt(p.MT, [&](auto mt) {
     split = sk5_kernel<decltype(mt)::value, true, 128, false>(tiles);
   });
-  run_reduce_add_rmsnorm(p, split, normed, x, w, ws, residual, nw, eps);
+  run_reduce_add_rmsnorm(p, bf16_gemm(p, nullptr, split, x, w), normed, ws,
+                         residual, nw, eps);
 }
 
 // The whole decode MLP tail in two kernels: silu(gate)*up happens in
@@ -1240,7 +1438,8 @@ void skinny_gemm5_silu_fused_norm(torch::Tensor normed, torch::Tensor gu,
   with_mt(p.MT, [&](auto mt) {
     split = sk5_kernel<decltype(mt)::value, true, 128, true>(tiles);
   });
-  run_reduce_add_rmsnorm(p, split, normed, gu, w, ws, residual, nw, eps);
+  run_reduce_add_rmsnorm(p, bf16_gemm(p, nullptr, split, gu, w), normed, ws,
+                         residual, nw, eps);
 }
 
 void skinny_gemm6(torch::Tensor out, torch::Tensor x, torch::Tensor w,
@@ -1259,7 +1458,65 @@ void skinny_gemm6(torch::Tensor out, torch::Tensor x, torch::Tensor w,
       split = skinny6_kernel<MT, true, 256>;
     }
   });
-  run_reduce(p, direct, split, out, x, w, ws);
+  run_reduce(p, bf16_gemm(p, direct, split, x, w), out, ws);
+}
+
+// ---- W8A16 entry points: fp8 weight bytes + per-row scales ----
+static void check_w8(const torch::Tensor& x, const torch::Tensor& q,
+                     const torch::Tensor& scale) {
+  TORCH_CHECK(x.dim() == 2 && q.dim() == 2 && x.size(1) == q.size(1),
+              "skinny gemm w8: x [M, K] and q [N, K]");
+  TORCH_CHECK(q.size(0) % 64 == 0 && q.size(1) % 64 == 0,
+              "skinny gemm w8: N%64, K%64");
+  TORCH_CHECK(q.scalar_type() == torch::kUInt8 &&
+              scale.scalar_type() == torch::kFloat32 &&
+              x.scalar_type() == torch::kBFloat16);
+  TORCH_CHECK(scale.numel() == q.size(0) && scale.is_contiguous() &&
+              q.is_contiguous());
+  TORCH_CHECK(x.is_cuda() && q.is_cuda() && scale.is_cuda());
+}
+
+static auto w8_gemm(const SkinnyPlan& p, const torch::Tensor& x,
+                    const torch::Tensor& q, const torch::Tensor& scale) {
+  return [=, &p](bool is_split, unsigned short* out, float* ws, dim3 grid,
+                 hipStream_t stream) {
+    const unsigned char* qp = q.data_ptr<unsigned char>();
+    const float* sp = scale.data_ptr<float>();
+    with_mt(p.MT, [&](auto mt) {
+      constexpr int MT = decltype(mt)::value;
+      if (is_split) {
+        skinny_w8_kernel<MT, true><<<grid, 256, 0, stream>>>(
+            out, ws, us_ptr(x), qp, sp, p.M, p.N, p.K);
+      } else {
+        skinny_w8_kernel<MT, false><<<grid, 256, 0, stream>>>(
+            out, ws, us_ptr(x), qp, sp, p.M, p.N, p.K);
+      }
+    });
+  };
+}
+
+void skinny_gemm_w8(torch::Tensor out, torch::Tensor x, torch::Tensor q,
+                    torch::Tensor scale, torch::Tensor ws) {
+  check_w8(x, q, scale);
+  check_plain(out, x, q, 64, 64);
+  TORCH_CHECK(out.scalar_type() == torch::kBFloat16 &&
+              out.numel() == x.size(0) * q.size(0));
+  const SkinnyPlan p = plan_w8(x.size(0), q.size(0), x.size(1));
+  run_reduce(p, w8_gemm(p, x, q, scale), out, ws);
+}
+
+void skinny_gemm_w8_fused_norm(torch::Tensor normed, torch::Tensor x,
+                               torch::Tensor q, torch::Tensor scale,
+                               torch::Tensor ws, torch::Tensor residual,
+                               torch::Tensor nw, double eps) {
+  check_w8(x, q, scale);
+  check_fused(normed, x, q, residual, x.size(1), 64);
+  TORCH_CHECK(normed.numel() == x.size(0) * q.size(0) &&
+              residual.numel() == normed.numel() &&
+              nw.numel() == q.size(0));
+  const SkinnyPlan p = plan_w8(x.size(0), q.size(0), x.size(1));
+  run_reduce_add_rmsnorm(p, w8_gemm(p, x, q, scale), normed, ws, residual,
+                         nw, eps);
 }
 
 }  // namespace kukeon

@@ -209,6 +209,37 @@ def linear_add_rmsnorm(x, w, residual, norm_weight, eps: float):
     return h
 
 
+E4M3_MAX = 448.0
+
+
+def quantize_fp8_rows(q: torch.Tensor, scale: torch.Tensor,
+                      w: torch.Tensor) -> None:
+    """Per-output-row fp8 weight quantisation: scale[n] = amax_n / 448
+    (1 for an all-zero row), q = rne_e4m3(w / scale) as uint8 e4m3fn."""
+    wf = w.float()
+    amax = wf.abs().amax(dim=1)
+    s = torch.where(amax > 0, amax / E4M3_MAX, torch.ones_like(amax))
+    scale.copy_(s)
+    # |w / s| <= 448 up to one rounding of the quotient; the clamp keeps
+    # that rounding away from the NaN encoding, like the kernel's
+    v = (wf / s[:, None]).clamp_(-E4M3_MAX, E4M3_MAX)
+    q.copy_(v.to(torch.float8_e4m3fn).view(torch.uint8))
+
+
+def dequant_fp8_rows(out: torch.Tensor, q: torch.Tensor,
+                     scale: torch.Tensor) -> None:
+    out.copy_((q.view(torch.float8_e4m3fn).float() *
+               scale[:, None]).to(out.dtype))
+
+
+def linear_w8(x: torch.Tensor, q: torch.Tensor,
+              scale: torch.Tensor) -> torch.Tensor:
+    """x @ deq(q, scale)^T in f32 on the exact (unrounded) dequantised
+    weight, rounded once to x's dtype."""
+    wf = q.view(torch.float8_e4m3fn).float() * scale[:, None]
+    return (x.float() @ wf.T).to(x.dtype)
+
+
 def decode_advance(ids, pos, seq_lens, tokens, ring, counter) -> None:
     step = int(counter[0])
     B = ids.shape[0]

@@ -190,6 +190,9 @@ class ModelhubServer:
                 "waiting": len(self.engine.waiting),
                 "kv_blocks_total": kv.num_blocks,
                 "kv_blocks_free": kv.allocator.num_free,
+                "weight_dtype": getattr(self.engine.model, "weight_dtype",
+                                        "bf16"),
+                "weight_bytes": _resident_weight_bytes(self.engine.model),
                 "turn_latency_ms": {"p50": pct(0.50), "p95": pct(0.95),
                                     "p99": pct(0.99),
                                     "n": len(lat)},
@@ -414,7 +417,14 @@ class ModelhubClient:
         self.sock.close()
 
 
-def main(argv: Optional[List[str]] = None) -> None:
+def _resident_weight_bytes(model) -> int:
+    fn = getattr(model, "resident_weight_bytes", None)
+    if fn is not None:
+        return int(fn())
+    return sum(p.numel() * p.element_size() for p in model.parameters())
+
+
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser("kukeon-modelhub")
     ap.add_argument("--model", default="llama-3-8b")
     ap.add_argument("--socket", default="/run/kukeon/modelhub.sock")
@@ -423,7 +433,15 @@ def main(argv: Optional[List[str]] = None) -> None:
     ap.add_argument("--max-sessions", type=int, default=256)
     ap.add_argument("--no-graphs", action="store_true")
     ap.add_argument("--kv-blocks", type=int, default=0)
-    args = ap.parse_args(argv)
+    ap.add_argument("--weight-dtype", choices=("bf16", "fp8"), default=None,
+                    help="GEMM weight storage; fp8 = e4m3 weight-only "
+                         "quantisation with per-output-channel scales "
+                         "(default: KUKEON_WEIGHT_DTYPE, else bf16)")
+    return ap
+
+
+def main(argv: Optional[List[str]] = None) -> None:
+    args = build_parser().parse_args(argv)
     from kukeon_amd.utils import logging as klog
     klog.setup(logging.INFO)
     import torch
@@ -435,10 +453,12 @@ def main(argv: Optional[List[str]] = None) -> None:
         use_graphs=not args.no_graphs and device != "cpu" and not cfg.is_moe)
     if cfg.is_moe:
         from kukeon_amd.models.mixtral import MixtralModel
-        model = MixtralModel(cfg, device=device)
+        model = MixtralModel(cfg, device=device,
+                             weight_dtype=args.weight_dtype)
     else:
         from kukeon_amd.models.llama import LlamaModel
-        model = LlamaModel(cfg, device=device)
+        model = LlamaModel(cfg, device=device,
+                           weight_dtype=args.weight_dtype)
     hub = ModelhubServer(model, cfg, ecfg, args.socket, device=device)
     hub.start()
     import signal
