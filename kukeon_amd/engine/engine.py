@@ -444,10 +444,14 @@ class LLMEngine:
         return self.Bmax
 
     def _decode_splits(self, bucket: int) -> int:
-        # target ~4096 split slots: the decode kernel runs B*Hk*S
-        # autonomous waves (4 per workgroup), and 4096 exactly fills the
-        # chip at its 4-waves/SIMD occupancy. A multiple of 4 keeps every
-        # workgroup's 4 waves busy (each owns one of 4 consecutive slots).
+        # target ~4096 split slots: the decode kernel runs B*Hk*S waves,
+        # one per slot, and 4096 exactly fills the chip at its
+        # 4-waves/SIMD occupancy. Launch plan (paged_attn.hip): S <= 4
+        # runs one 4-wave workgroup per (sequence, kv head), 5..8 one
+        # 8-wave workgroup, and that workgroup merges its own splits —
+        # decode attention is a single launch. S > 8 (buckets below 64
+        # here) runs 4-wave workgroups into the workspaces plus the reduce
+        # kernel. A multiple of 4 keeps every workgroup's waves busy.
         want = (16 * 256 + bucket * self.hk - 1) // (bucket * self.hk)
         return max(4, min(self.max_splits, ((want + 3) // 4) * 4))
 

@@ -124,38 +124,30 @@ class LlamaAttention(nn.Module):
         self.o_w = _make_weight((cfg.hidden_size, self.hq * self.d), device,
                                 weight_dtype)
 
-    def forward(self, x: torch.Tensor, cos_sin: torch.Tensor,
+    def _attend(self, x: torch.Tensor, cos_sin: torch.Tensor,
                 kc: torch.Tensor, vc: torch.Tensor, meta: AttnMeta):
+        """qkv projection, RoPE, KV append and attention. Decode runs the
+        last three as one kernel (ops.paged_attention_rope), which leaves
+        qkv unrotated — nothing below reads q or k from it again."""
         qkv = ops.linear(x, self.qkv_w)
+        out = torch.empty(x.shape[0], self.hq * self.d, dtype=x.dtype,
+                          device=x.device)
+        # an fp8 cache stays on the separate launches: its attention kernel
+        # is bound by the fp8 -> bf16 conversions and the fused variant of
+        # it measured 1-7% behind the sequence in most buckets
+        # (docs/perf.md); paged_attention still merges in the workgroup
+        if (meta.mode == "decode" and ops.DECODE_ATTN_FUSED
+                and kc.dtype != torch.uint8):
+            ops.paged_attention_rope(out, qkv, kc, vc, cos_sin,
+                                     meta.positions, meta.block_table,
+                                     meta.seq_lens, self.hq, self.hk,
+                                     meta.num_splits, self.scale,
+                                     meta.tmp_out, meta.tmp_ml)
+            return out
         ops.rope_kv_append(qkv, kc, vc, cos_sin, meta.positions,
                            meta.slot_mapping, self.hq, self.hk, self.d,
                            block_table=(meta.block_table
                                         if meta.mode == "decode" else None))
-        out = torch.empty(x.shape[0], self.hq * self.d, dtype=x.dtype,
-                          device=x.device)
-        if meta.mode == "decode":
-            ops.paged_attention(out, qkv, kc, vc, meta.block_table,
-                                meta.seq_lens, 0, meta.num_splits, self.scale,
-                                meta.tmp_out, meta.tmp_ml)
-        else:
-            ops.prefill_attention(out, qkv, kc, vc, meta.block_table,
-                                  meta.seq_lens, meta.q_starts, meta.qb_seq,
-                                  meta.qb_start, 0, self.scale)
-        o = ops.linear(out, self.o_w)
-        return parallel.tp_all_reduce(o)
-
-    def forward_pre_o(self, x: torch.Tensor, cos_sin: torch.Tensor,
-                      kc: torch.Tensor, vc: torch.Tensor, meta: AttnMeta):
-        """Attention WITHOUT the output projection: the layer fuses the
-        o-proj with the post-attention add+RMSNorm (one epilogue kernel
-        instead of reduce + norm)."""
-        qkv = ops.linear(x, self.qkv_w)
-        ops.rope_kv_append(qkv, kc, vc, cos_sin, meta.positions,
-                           meta.slot_mapping, self.hq, self.hk, self.d,
-                           block_table=(meta.block_table
-                                        if meta.mode == "decode" else None))
-        out = torch.empty(x.shape[0], self.hq * self.d, dtype=x.dtype,
-                          device=x.device)
         if meta.mode == "decode":
             ops.paged_attention(out, qkv, kc, vc, meta.block_table,
                                 meta.seq_lens, 0, meta.num_splits, self.scale,
@@ -165,6 +157,19 @@ class LlamaAttention(nn.Module):
                                   meta.seq_lens, meta.q_starts, meta.qb_seq,
                                   meta.qb_start, 0, self.scale)
         return out
+
+    def forward(self, x: torch.Tensor, cos_sin: torch.Tensor,
+                kc: torch.Tensor, vc: torch.Tensor, meta: AttnMeta):
+        out = self._attend(x, cos_sin, kc, vc, meta)
+        o = ops.linear(out, self.o_w)
+        return parallel.tp_all_reduce(o)
+
+    def forward_pre_o(self, x: torch.Tensor, cos_sin: torch.Tensor,
+                      kc: torch.Tensor, vc: torch.Tensor, meta: AttnMeta):
+        """Attention WITHOUT the output projection: the layer fuses the
+        o-proj with the post-attention add+RMSNorm (one epilogue kernel
+        instead of reduce + norm)."""
+        return self._attend(x, cos_sin, kc, vc, meta)
 
 
 class LlamaMLP(nn.Module):

@@ -91,6 +91,30 @@ def paged_attention(out, q, k_cache, v_cache, block_table, seq_lens,
                              q_offset, num_splits, scale, tmp_out, tmp_ml)
 
 
+# KUKEON_DECODE_ATTN_FUSED=0 makes the models' decode path run
+# rope_kv_append + paged_attention as separate launches again (A/B
+# measurement, tests); the default folds both into paged_attention_rope.
+DECODE_ATTN_FUSED = __import__("os").environ.get(
+    "KUKEON_DECODE_ATTN_FUSED", "1") != "0"
+
+
+def paged_attention_rope(out, qkv, k_cache, v_cache, cos_sin, positions,
+                         block_table, seq_lens, num_q_heads: int,
+                         num_kv_heads: int, num_splits: int, scale: float,
+                         tmp_out, tmp_ml) -> None:
+    """rope_kv_append (block-table mode) + paged_attention of one decode
+    token per row of the fused `qkv` projection, in one pass: q and the new
+    k are rotated on the fly, the new k/v rows are appended to the caches,
+    and `out` is what the two ops would have produced, bit for bit. `qkv`
+    itself is left untouched. A row with positions < 0 appends nothing;
+    workspaces and seq_len <= 0 as in paged_attention (with num_splits <= 8
+    the GPU kernel does not touch the workspaces at all)."""
+    _impl(qkv).paged_attention_rope(out, qkv, k_cache, v_cache, cos_sin,
+                                    positions, block_table, seq_lens,
+                                    num_q_heads, num_kv_heads, num_splits,
+                                    scale, tmp_out, tmp_ml)
+
+
 def prefill_attention(out, q, k_cache, v_cache, block_table, seq_lens,
                       q_starts, qb_seq, qb_start, q_offset: int,
                       scale: float) -> None:

@@ -20,6 +20,13 @@ void paged_attention(torch::Tensor out, torch::Tensor q, torch::Tensor k_cache,
                      torch::Tensor seq_lens, int64_t q_offset,
                      int64_t num_splits, double scale, torch::Tensor tmp_out,
                      torch::Tensor tmp_ml);
+void paged_attention_rope(torch::Tensor out, torch::Tensor qkv,
+                          torch::Tensor k_cache, torch::Tensor v_cache,
+                          torch::Tensor cos_sin, torch::Tensor positions,
+                          torch::Tensor block_table, torch::Tensor seq_lens,
+                          int64_t num_q_heads, int64_t num_kv_heads,
+                          int64_t num_splits, double scale,
+                          torch::Tensor tmp_out, torch::Tensor tmp_ml);
 void prefill_attention(torch::Tensor out, torch::Tensor q,
                        torch::Tensor k_cache, torch::Tensor v_cache,
                        torch::Tensor block_table, torch::Tensor seq_lens,
@@ -88,6 +95,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "in-place NEOX RoPE on fused qkv + paged KV append");
   m.def("paged_attention", &kukeon::paged_attention,
         "decode paged attention (GQA, split-KV)");
+  m.def("paged_attention_rope", &kukeon::paged_attention_rope,
+        "decode paged attention with RoPE + KV append folded in");
   m.def("prefill_attention", &kukeon::prefill_attention,
         "varlen causal paged prefill attention (MFMA)");
   m.def("mfma_probe", &kukeon::mfma_probe,

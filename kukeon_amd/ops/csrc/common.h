@@ -56,6 +56,22 @@ DEV_INLINE uint4 pack_bf16x8(const float* f) {
   return r;
 }
 
+// NEOX half-rotation of 8 (x, y) pairs in f32: co / si point at the pairs'
+// cos and sin entries. Shared by rope_kv_kernel and the decode attention
+// kernel, which must round alike bit for bit, so the FMA contraction is
+// written out instead of left to the call site's optimiser. The caller
+// rounds xo / yo (pack_bf16x8, pack_fp8x8).
+DEV_INLINE void rope_rotate8(const bf16x8& x, const bf16x8& y,
+                             const float* co, const float* si, float* xo,
+                             float* yo) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const float c = co[j], s = si[j];
+    xo[j] = __builtin_fmaf(x.f(j), c, -(y.f(j) * s));
+    yo[j] = __builtin_fmaf(x.f(j), s, y.f(j) * c);
+  }
+}
+
 // ---------- fp8 (OCP e4m3fn) helpers ----------
 typedef __attribute__((__vector_size__(2 * sizeof(float)))) float f32x2_cvt_t;
 

@@ -1,8 +1,11 @@
 // Paged decode attention for gfx950 (MI355X): one query token per
 // sequence against a paged KV cache, split-KV (flash-decode) on the matrix
-// cores. One attention kernel plus one reduce, always run as a pair.
+// cores. One attention kernel; decode runs it as ONE launch whenever the
+// splits of a sequence fit in one workgroup (S <= 8), else as a pair with
+// the reduce kernel.
 //
-// paged_attn_kernel — grid (B, Hk, ceil(S/4)), 4 waves per workgroup.
+// paged_attn_kernel<FP8, ROPE> — grid (B, Hk, ceil(S/NW)), NW waves per
+//   workgroup: NW = 4 for S <= 4 and for S > 8, NW = 8 for 5 <= S <= 8.
 //   The whole GQA group (G = Hq/Hk <= 16 q-heads sharing one kv-head)
 //   rides the MFMA N axis, so each K/V block is read from HBM once per
 //   group — KV bandwidth is the decode cost, never multiply it by G.
@@ -15,47 +18,104 @@
 //       In this swapped shape the C layout of the scores IS the B layout
 //       of P, so P needs no cross-lane redistribution at all, just two
 //       v_cvt_pk_bf16_f32.
-//     - 8 KiB LDS per wave (32 KiB per workgroup), no barriers.
+//     - 8 KiB LDS per wave (dynamic: 32 KiB at NW = 4, 64 KiB at NW = 8,
+//       so a CU holds 16 waves either way), no barriers in the tile loop.
 //
 // Split slots. The KV blocks of a sequence are cut into S contiguous
 //   ranges ("slots") of ceil(nblocks/S) blocks; a slot past the end has an
-//   empty range. The 4 waves of a workgroup are fully autonomous: wave w
-//   of workgroup z owns slot 4*z + w, walks that range alone and writes
-//   its unnormalized O (f32) and (m, l) into tmp_out / tmp_ml at that
-//   slot. Waves whose slot is >= S do nothing. Every slot < S is written
-//   on every call (an empty range writes O = 0, m = -inf, l = 0), which is
-//   what lets the reduce read all S slots unconditionally.
+//   empty range. Wave w of workgroup z owns slot NW*z + w and walks that
+//   range alone. No workgroup ever waits for, signals or reads another:
+//   there are no atomics, counters or flags anywhere in this file.
 //
-// paged_attn_reduce_kernel — grid (B, Hq), 128 threads: merges the S
-//   partials of one head and writes the bf16 output row.
+// ROPE (ops.paged_attention_rope; q is the fused qkv row, untouched):
+//   - Q is rotated in registers. qf[st] holds dims st*32 + g4*8..+7, the
+//     x half for st = 0,1 and the matching y half for st = 2,3, so the
+//     NEOX rotation is lane-local; rope_rotate8 (common.h) rounds exactly
+//     as rope_kv_kernel does.
+//   - The new token's K row (rotated) and V row are appended to the cache
+//     by the one wave whose slot range holds block pos/16 — the only wave
+//     that reads that row, so no other wave depends on the write. It
+//     stores, issues __threadfence_block(), and only then loads K/V, so
+//     what it attends to is what the cache holds (fp8 rounding included).
+//     If no slot holds the block (ctx <= 0, or pos/16 >= nblocks) slot
+//     0's wave appends and nobody reads it; pos < 0 appends nothing.
+//
+// Merge. When S <= NW (one workgroup per (b, hk)) the waves park their
+//   unnormalised O and (m, l) in the V^T buffers, which are dead by then,
+//   and wave 0 computes the output rows with the loop order and
+//   expressions of paged_attn_reduce_kernel (merge_weight / fmaf below),
+//   bit-equal to the two-kernel path; tmp_out / tmp_ml are not touched.
+//   Wave 0 keeps its own O in registers: with G = 16 the other waves' O
+//   fills their 8 KiB exactly, and wave 0's buffer takes every (m, l).
+//   Otherwise each wave writes its partial into tmp_out / tmp_ml at its
+//   slot — every slot < S on every call (an empty range writes O = 0,
+//   m = -inf, l = 0), which lets paged_attn_reduce_kernel — grid (B, Hq),
+//   128 threads — read all S slots unconditionally.
 //
 // A row with seq_len <= 0 is skipped by both kernels: its `out` row (and
-//   its workspace slots) are left untouched.
+//   its workspace slots) are left untouched (ROPE still appends).
+//
+// Hazards this kernel is written around:
+//   - Non-uniform barrier. The merge path has two __syncthreads(). The only
+//     returns before them are `ctx <= 0` (b is per workgroup: uniform) and
+//     the non-merge path (`merge` is a kernel argument: uniform). A wave
+//     whose slot is >= S, and the padding lanes rc >= G, are NOT returned
+//     early on the merge path: their block range is empty, they fall
+//     through the tile loop to the barriers and write nothing. The append
+//     runs before any of this and contains no barrier.
+//   - NaN in the cache. Stale cache rows may hold NaN, and the new token's
+//     row does until the append. The score mask (-inf) and the V-row
+//     zeroing are keyed on kv_hi as before; the append precedes the first
+//     K/V load of the wave that reads the row.
+//   - Graph replay. positions / seq_lens / block_table are read on the
+//     device at every launch; the op keeps no host state and allocates
+//     nothing.
+//   - Register budget. __launch_bounds__ keeps 128 VGPRs (4 waves/SIMD)
+//     for bf16 and fp8 alike, spill-free; the RoPE / append prologue and
+//     the merge epilogue live outside the tile loop.
+//   - Bit-equal RoPE: rope_rotate8 pins the FMA contraction for both
+//     kernels.
 //
 // Two designs were measured against this one and removed; their code is in
-// this commit's parent. A v_dot2 kernel (workgroup per split, K/V staged in
-// LDS, packed-bf16 dot products) was issue-stall bound — ~28 dependent VALU
-// instructions per KV token, 3.8-4.1 TB/s against 4.9-5.4 here. A 32-token
-// 32x32x16 MFMA tile was LDS-residency bound — 64 KiB per workgroup caps a
-// CU at 2 workgroups, 25-30% behind end to end.
+// the history of this file. A v_dot2 kernel (workgroup per split, K/V
+// staged in LDS, packed-bf16 dot products) was issue-stall bound — ~28
+// dependent VALU instructions per KV token, 3.8-4.1 TB/s against 4.9-5.4
+// here. A 32-token 32x32x16 MFMA tile was LDS-residency bound — 64 KiB per
+// 4-wave workgroup capped a CU at 8 waves, 25-30% behind end to end.
 #include "attn_frag.h"
 #include <torch/extension.h>
 #include <c10/hip/HIPStream.h>
 
 namespace kukeon {
 
-template <bool FP8>
-// fp8 needs headroom for the cvt_pk conversions (at 4 waves/SIMD the
-// 128-reg bound put a 2-VGPR spill in the hot loop)
-__global__ __launch_bounds__(256, FP8 ? 3 : 4) void paged_attn_kernel(
+// Weight of split s in the merge; shared by the reduce kernel and the
+// in-workgroup merge so both round alike.
+DEV_INLINE float merge_weight(float m_s, float M) {
+  return m_s == -INFINITY ? 0.f : __expf(m_s - M);
+}
+
+constexpr int kWaveLds = 2 * 128 * 16 * 2;  // two V^T images: 8 KiB
+
+template <bool FP8, bool ROPE>
+// 128 VGPRs (4 waves/SIMD) for both cache types. fp8 used to be bounded at
+// 3 waves/SIMD for headroom but compiled to 127 registers and so ran at 4;
+// with the prologue added here the looser bound let it drift to 131, which
+// really is 3 waves/SIMD (one 8-wave workgroup per CU) and cost 10% of the
+// fp8-KV benchmark. At this bound it builds to 128 with no spill; check the
+// resource usage again after any change to the tile loop.
+__global__ __launch_bounds__(512, 4) void paged_attn_kernel(
+    unsigned short* __restrict__ out,     // [B, Hq*D] (merge path)
     float* __restrict__ tmp_out,          // [B, Hq, S, D] f32
     float* __restrict__ tmp_ml,           // [B, Hq, S, 2]
-    const unsigned short* __restrict__ q, // [B, q_stride]
-    const void* __restrict__ k_cache,     // [NB, Hk, 16, D]
-    const void* __restrict__ v_cache,
+    const unsigned short* __restrict__ q, // [B, q_stride]; ROPE: qkv rows
+    void* k_cache,                        // [NB, Hk, 16, D]; ROPE appends,
+    void* v_cache,                        //   so not __restrict__
+    const float* __restrict__ cos_sin,    // [max_pos, D]   (ROPE)
+    const int* __restrict__ positions,    // [B]            (ROPE)
     const int* __restrict__ block_table,  // [B, max_blocks]
     const int* __restrict__ seq_lens,     // [B]
-    long q_stride, int Hq, int Hk, int max_blocks, int S, float scale) {
+    long q_stride, int Hq, int Hk, int max_blocks, int S, int merge,
+    float scale) {
   constexpr int D = 128;
   constexpr int BS = 16;
   const int b = blockIdx.x;
@@ -65,19 +125,66 @@ __global__ __launch_bounds__(256, FP8 ? 3 : 4) void paged_attn_kernel(
   const int g4 = lane >> 4;       // 0..3
   const int rc = lane & 15;
   const int G = Hq / Hk;
-  const int slot = blockIdx.z * 4 + wid;
+  const int slot = blockIdx.z * (blockDim.x / WAVE) + wid;
   const int ctx = seq_lens[b];
-  if (ctx <= 0 || slot >= S) return;
+
+  const int nblocks = ctx > 0 ? (ctx + BS - 1) / BS : 0;
+  const int per_slot = (nblocks + S - 1) / S;
+
+  const int pos = ROPE ? positions[b] : -1;
+  if (ROPE && pos >= 0) {
+    // ---- rotate K + append K/V: the one wave that will read the row ----
+    const int pblk = pos / BS;
+    const int owner = pblk < nblocks ? pblk / per_slot : 0;
+    if (slot == owner && pblk < max_blocks && lane < 16) {
+      const unsigned short* krow =
+          q + (long)b * q_stride + (long)(Hq + hk) * D;
+      const unsigned short* vrow = krow + (long)Hk * D;
+      const long dst =
+          (((long)block_table[(long)b * max_blocks + pblk] * Hk + hk) * BS +
+           pos % BS) * D;
+      auto* kdst = reinterpret_cast<kv_elem_t<FP8>*>(k_cache) + dst;
+      auto* vdst = reinterpret_cast<kv_elem_t<FP8>*>(v_cache) + dst;
+      if (lane < 8) {  // 8 pairs per lane
+        const int d0 = lane * 8;
+        const float* cs = cos_sin + (long)pos * D;
+        float xo[8], yo[8];
+        rope_rotate8(load_bf16x8(krow + d0), load_bf16x8(krow + D / 2 + d0),
+                     cs + d0, cs + D / 2 + d0, xo, yo);
+        if constexpr (FP8) {
+          *reinterpret_cast<uint2*>(kdst + d0) = pack_fp8x8(xo);
+          *reinterpret_cast<uint2*>(kdst + D / 2 + d0) = pack_fp8x8(yo);
+        } else {
+          *reinterpret_cast<uint4*>(kdst + d0) = pack_bf16x8(xo);
+          *reinterpret_cast<uint4*>(kdst + D / 2 + d0) = pack_bf16x8(yo);
+        }
+      }
+      const bf16x8 v = load_bf16x8(vrow + lane * 8);
+      if constexpr (FP8) {
+        float f[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) f[j] = v.f(j);
+        *reinterpret_cast<uint2*>(vdst + lane * 8) = pack_fp8x8(f);
+      } else {
+        *reinterpret_cast<uint4*>(vdst + lane * 8) = v.raw;
+      }
+    }
+    // the appending wave is the row's only reader: order its stores
+    // before its own K/V loads
+    __threadfence_block();
+  }
+  // uniform per workgroup; a wave with slot >= S leaves only where no
+  // barrier follows (on the merge path its range below is empty)
+  if (ctx <= 0 || (!merge && slot >= S)) return;
 
   // V^T images only — K is consumed straight from HBM in fragment shape
   // (16 B/lane across 64 B-line groups; the LDS round trip was pure
   // added latency here: per-wave parked time was 67% of cycles). Two
   // V^T buffers per wave: tile bi's image is written during tile bi-1,
   // so PV never waits on fresh LDS stores.
-  __shared__ __align__(16) unsigned short vtbuf[4][2][D * BS];
+  extern __shared__ __align__(16) unsigned short vtbuf_all[];
+  unsigned short* const vtbuf0 = vtbuf_all + wid * (2 * D * BS);
 
-  const int nblocks = (ctx + BS - 1) / BS;
-  const int per_slot = (nblocks + S - 1) / S;
   const int blk_begin = slot * per_slot;
   const int blk_end = min(nblocks, blk_begin + per_slot);
   const int kv_hi = min(ctx, blk_end * BS);
@@ -89,9 +196,25 @@ __global__ __launch_bounds__(256, FP8 ? 3 : 4) void paged_attn_kernel(
   {
     const unsigned short* qp =
         q + (long)b * q_stride + (long)(hk * G + qh) * D;
+    bf16x8 qv[4];
+#pragma unroll
+    for (int st = 0; st < 4; ++st)
+      qv[st] = load_bf16x8(qp + st * 32 + g4 * 8);
+    if (ROPE && pos >= 0) {
+      // qv[st] / qv[st + 2] are the x / y halves of the same 8 pairs
+      const float* cs = cos_sin + (long)pos * D;
+#pragma unroll
+      for (int st = 0; st < 2; ++st) {
+        const int d0 = st * 32 + g4 * 8;
+        float xo[8], yo[8];
+        rope_rotate8(qv[st], qv[st + 2], cs + d0, cs + D / 2 + d0, xo, yo);
+        qv[st].raw = pack_bf16x8(xo);
+        qv[st + 2].raw = pack_bf16x8(yo);
+      }
+    }
 #pragma unroll
     for (int st = 0; st < 4; ++st) {
-      const uint4 v = *reinterpret_cast<const uint4*>(qp + st * 32 + g4 * 8);
+      const uint4 v = qv[st].raw;
       qf[st][0] = v.x; qf[st][1] = v.y; qf[st][2] = v.z; qf[st][3] = v.w;
     }
   }
@@ -157,12 +280,12 @@ __global__ __launch_bounds__(256, FP8 ? 3 : 4) void paged_attn_kernel(
   if (blk_begin < blk_end) {
     kfetch(blk_begin);
     vfetch(blk_begin);
-    vwrite(vtbuf[wid][blk_begin & 1], blk_begin * BS);
+    vwrite(vtbuf0 + (blk_begin & 1) * (D * BS), blk_begin * BS);
   }
 
   for (int bi = blk_begin; bi < blk_end; ++bi) {
     const int kvbase = bi * BS;
-    const unsigned short* vt = vtbuf[wid][bi & 1];
+    const unsigned short* vt = vtbuf0 + (bi & 1) * (D * BS);
 
     // ---- S^T = K . Q^T from the in-flight K fragments ----
     f32x4_t sacc = {};
@@ -208,7 +331,7 @@ __global__ __launch_bounds__(256, FP8 ? 3 : 4) void paged_attn_kernel(
     // ---- stage NEXT tile's V^T into the other buffer ----
     if (bi + 1 < blk_end) {
       vfetch(bi + 1);
-      vwrite(vtbuf[wid][(bi + 1) & 1], (bi + 1) * BS);
+      vwrite(vtbuf0 + ((bi + 1) & 1) * (D * BS), (bi + 1) * BS);
     }
 
     // ---- PV: P is already a 16x16x16 B fragment ----
@@ -225,21 +348,84 @@ __global__ __launch_bounds__(256, FP8 ? 3 : 4) void paged_attn_kernel(
     }
   }
 
-  // ---- epilogue: unnormalized O + (m, l) into this wave's slot ----
-  if (rc >= G) return;
-  const int head = hk * G + rc;
-  float* top = tmp_out + (((long)b * Hq + head) * S + slot) * D;
+  if (!merge) {
+    // ---- epilogue: unnormalized O + (m, l) into this wave's slot ----
+    if (rc >= G) return;
+    const int head = hk * G + rc;
+    float* top = tmp_out + (((long)b * Hq + head) * S + slot) * D;
 #pragma unroll
-  for (int dc = 0; dc < 8; ++dc) {
+    for (int dc = 0; dc < 8; ++dc) {
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      top[dc * 16 + 4 * g4 + r] = oacc[dc][r];
+      for (int r = 0; r < 4; ++r) {
+        top[dc * 16 + 4 * g4 + r] = oacc[dc][r];
+      }
+    }
+    if (g4 == 0) {
+      float* ml = tmp_ml + (((long)b * Hq + head) * S + slot) * 2;
+      ml[0] = m;
+      ml[1] = l_acc;
+    }
+    return;
+  }
+
+  // ---- merge inside the workgroup (S <= waves; EVERY wave gets here) ----
+  // LDS after the first barrier: wave w >= 1 parks O in its own 8 KiB as
+  // [head][32 float4], the float4 index XOR-ed with the head so the 16
+  // heads of a store or load spread over the banks; wave 0's 8 KiB takes
+  // (m, l) of every wave as [w][head] float2.
+  char* const lds = reinterpret_cast<char*>(vtbuf_all);
+  __syncthreads();  // all tile loops done: the V^T images are dead
+  if (rc < G && slot < S) {
+    if (wid > 0) {
+      float4* op = reinterpret_cast<float4*>(lds + wid * kWaveLds + rc * 512);
+#pragma unroll
+      for (int dc = 0; dc < 8; ++dc)
+        op[(dc * 4 + g4) ^ rc] =
+            float4{oacc[dc][0], oacc[dc][1], oacc[dc][2], oacc[dc][3]};
+    }
+    if (g4 == 0)
+      reinterpret_cast<float2*>(lds)[wid * 16 + rc] = float2{m, l_acc};
+  }
+  __syncthreads();
+  if (wid != 0 || rc >= G) return;
+  // same loop order and expressions as paged_attn_reduce_kernel
+  const float2* ml = reinterpret_cast<const float2*>(lds) + rc;
+  float M = -INFINITY;
+  for (int s = 0; s < S; ++s) M = fmaxf(M, ml[s * 16].x);
+  float L = 0.f;
+  for (int s = 0; s < S; ++s)
+    L = __builtin_fmaf(merge_weight(ml[s * 16].x, M), ml[s * 16].y, L);
+  f32x4_t acc[8];
+  {
+    const float w = merge_weight(ml[0].x, M);
+#pragma unroll
+    for (int dc = 0; dc < 8; ++dc)
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        acc[dc][r] = __builtin_fmaf(w, oacc[dc][r], 0.f);
+  }
+  for (int s = 1; s < S; ++s) {
+    const float w = merge_weight(ml[s * 16].x, M);
+    const float4* op =
+        reinterpret_cast<const float4*>(lds + s * kWaveLds + rc * 512);
+#pragma unroll
+    for (int dc = 0; dc < 8; ++dc) {
+      const float4 o = op[(dc * 4 + g4) ^ rc];
+      acc[dc][0] = __builtin_fmaf(w, o.x, acc[dc][0]);
+      acc[dc][1] = __builtin_fmaf(w, o.y, acc[dc][1]);
+      acc[dc][2] = __builtin_fmaf(w, o.z, acc[dc][2]);
+      acc[dc][3] = __builtin_fmaf(w, o.w, acc[dc][3]);
     }
   }
-  if (g4 == 0) {
-    float* ml = tmp_ml + (((long)b * Hq + head) * S + slot) * 2;
-    ml[0] = m;
-    ml[1] = l_acc;
+  unsigned short* orow = out + (long)b * Hq * D + (long)(hk * G + rc) * D;
+#pragma unroll
+  for (int dc = 0; dc < 8; ++dc) {
+    unsigned short e[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) e[r] = f2us(L > 0.f ? acc[dc][r] / L : 0.f);
+    *reinterpret_cast<uint2*>(orow + dc * 16 + 4 * g4) =
+        uint2{(unsigned)e[0] | ((unsigned)e[1] << 16),
+              (unsigned)e[2] | ((unsigned)e[3] << 16)};
   }
 }
 
@@ -260,24 +446,29 @@ __global__ void paged_attn_reduce_kernel(
   for (int s = 0; s < S; ++s) M = fmaxf(M, ml[s * 2]);
   float L = 0.f;
   for (int s = 0; s < S; ++s)
-    L += (ml[s * 2] == -INFINITY ? 0.f : __expf(ml[s * 2] - M)) *
-         ml[s * 2 + 1];
+    L = __builtin_fmaf(merge_weight(ml[s * 2], M), ml[s * 2 + 1], L);
   const float* top = tmp_out + (((long)b * Hq + h) * S) * D;
   float acc = 0.f;
   for (int s = 0; s < S; ++s) {
-    const float w = ml[s * 2] == -INFINITY ? 0.f : __expf(ml[s * 2] - M);
-    acc += w * top[(long)s * D + d];
+    const float w = merge_weight(ml[s * 2], M);
+    acc = __builtin_fmaf(w, top[(long)s * D + d], acc);
   }
   out[(long)b * Hq * D + (long)h * D + d] = f2us(L > 0.f ? acc / L : 0.f);
 }
 
 // out[b] = attention(q[b, q_offset : q_offset + Hq*128], cache blocks of b)
-// for b in [0, q.size(0)). All checks are on host-side metadata.
-void paged_attention(torch::Tensor out, torch::Tensor q, torch::Tensor k_cache,
-                     torch::Tensor v_cache, torch::Tensor block_table,
-                     torch::Tensor seq_lens, int64_t q_offset,
-                     int64_t num_splits, double scale, torch::Tensor tmp_out,
-                     torch::Tensor tmp_ml) {
+// for b in [0, q.size(0)). With cos_sin / positions (both or neither) q is
+// the fused qkv projection [B, (Hq+2*Hk)*128]: q and the new k are rotated
+// on the fly and the new k/v rows appended to the caches; qkv itself is
+// not written. All checks are on host-side metadata; nothing is allocated.
+static void decode_attention(torch::Tensor out, torch::Tensor q,
+                             torch::Tensor k_cache, torch::Tensor v_cache,
+                             const torch::Tensor* cos_sin,
+                             const torch::Tensor* positions,
+                             torch::Tensor block_table, torch::Tensor seq_lens,
+                             int64_t q_offset, int64_t num_splits,
+                             double scale, torch::Tensor tmp_out,
+                             torch::Tensor tmp_ml) {
   const int B = q.size(0);
   if (B == 0) return;
   TORCH_CHECK(k_cache.dim() == 4 && k_cache.size(2) == 16 &&
@@ -331,21 +522,81 @@ void paged_attention(torch::Tensor out, torch::Tensor q, torch::Tensor k_cache,
     TORCH_CHECK(t.device() == q.device() && t.is_cuda(),
                 "all tensors must be on the same GPU");
 
+  const bool rope = cos_sin != nullptr;
+  const float* csp = nullptr;
+  const int* posp = nullptr;
+  if (rope) {
+    TORCH_CHECK(q_offset == 0 && q.is_contiguous() &&
+                    q.size(1) == (int64_t)(Hq + 2 * Hk) * D,
+                "qkv must be contiguous bf16 [B, (Hq+2*Hk)*128]");
+    TORCH_CHECK(cos_sin->scalar_type() == torch::kFloat32 &&
+                    cos_sin->dim() == 2 && cos_sin->size(1) == D &&
+                    cos_sin->is_contiguous(),
+                "cos_sin must be contiguous float32 [max_pos, 128]");
+    TORCH_CHECK(positions->scalar_type() == torch::kInt32 &&
+                    positions->is_contiguous() && positions->numel() >= B,
+                "positions must be contiguous int32 [>= B]");
+    for (const auto* t : {cos_sin, positions})
+      TORCH_CHECK(t->device() == q.device(),
+                  "all tensors must be on the same GPU");
+    csp = cos_sin->data_ptr<float>();
+    posp = positions->data_ptr<int>();
+  }
+
+  // Launch plan: all S slots of a (sequence, kv head) in one workgroup of
+  // 4 or 8 waves when they fit — that workgroup merges them itself — else
+  // 4-wave workgroups into the workspaces plus the reduce kernel.
+  const int S = (int)num_splits;
+  const bool merge = S <= 8;
+  const int waves = merge && S > 4 ? 8 : 4;
   auto stream = c10::hip::getCurrentHIPStream().stream();
   const unsigned short* qp =
       reinterpret_cast<const unsigned short*>(q.data_ptr()) + q_offset;
-  auto* launch = fp8 ? paged_attn_kernel<true> : paged_attn_kernel<false>;
-  launch<<<dim3(B, Hk, (unsigned)((num_splits + 3) / 4)), 256, 0, stream>>>(
+  auto* launch = fp8 ? (rope ? paged_attn_kernel<true, true>
+                             : paged_attn_kernel<true, false>)
+                     : (rope ? paged_attn_kernel<false, true>
+                             : paged_attn_kernel<false, false>);
+  launch<<<dim3(B, Hk, (unsigned)((S + waves - 1) / waves)), waves * WAVE,
+           waves * kWaveLds, stream>>>(
+      reinterpret_cast<unsigned short*>(out.data_ptr()),
       tmp_out.data_ptr<float>(), tmp_ml.data_ptr<float>(), qp,
-      k_cache.data_ptr(), v_cache.data_ptr(), block_table.data_ptr<int>(),
-      seq_lens.data_ptr<int>(), q.stride(0), Hq, Hk,
-      (int)block_table.size(1), (int)num_splits, (float)scale);
+      k_cache.data_ptr(), v_cache.data_ptr(), csp, posp,
+      block_table.data_ptr<int>(), seq_lens.data_ptr<int>(), q.stride(0), Hq,
+      Hk, (int)block_table.size(1), S, (int)merge, (float)scale);
   HIP_CHECK_KERNEL();
+  if (merge) return;
   paged_attn_reduce_kernel<128><<<dim3(B, Hq), 128, 0, stream>>>(
       reinterpret_cast<unsigned short*>(out.data_ptr()),
       tmp_out.data_ptr<float>(), tmp_ml.data_ptr<float>(),
-      seq_lens.data_ptr<int>(), Hq, (int)num_splits);
+      seq_lens.data_ptr<int>(), Hq, S);
   HIP_CHECK_KERNEL();
+}
+
+void paged_attention(torch::Tensor out, torch::Tensor q, torch::Tensor k_cache,
+                     torch::Tensor v_cache, torch::Tensor block_table,
+                     torch::Tensor seq_lens, int64_t q_offset,
+                     int64_t num_splits, double scale, torch::Tensor tmp_out,
+                     torch::Tensor tmp_ml) {
+  decode_attention(out, q, k_cache, v_cache, nullptr, nullptr, block_table,
+                   seq_lens, q_offset, num_splits, scale, tmp_out, tmp_ml);
+}
+
+// rope_kv_append (table mode) + paged_attention in one pass over one decode
+// token per row of the fused qkv projection; see the header comment.
+void paged_attention_rope(torch::Tensor out, torch::Tensor qkv,
+                          torch::Tensor k_cache, torch::Tensor v_cache,
+                          torch::Tensor cos_sin, torch::Tensor positions,
+                          torch::Tensor block_table, torch::Tensor seq_lens,
+                          int64_t num_q_heads, int64_t num_kv_heads,
+                          int64_t num_splits, double scale,
+                          torch::Tensor tmp_out, torch::Tensor tmp_ml) {
+  TORCH_CHECK(out.dim() == 2 && out.size(1) == num_q_heads * 128 &&
+                  k_cache.dim() == 4 && k_cache.size(1) == num_kv_heads,
+              "out must be [B, num_q_heads*128] and the caches "
+              "[NB, num_kv_heads, 16, 128]");
+  decode_attention(out, qkv, k_cache, v_cache, &cos_sin, &positions,
+                   block_table, seq_lens, 0, num_splits, scale, tmp_out,
+                   tmp_ml);
 }
 
 }  // namespace kukeon

@@ -54,12 +54,7 @@ __global__ void rope_kv_kernel(
     bf16x8 x = load_bf16x8(base + d0);
     bf16x8 y = load_bf16x8(base + half + d0);
     float xo[8], yo[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float co = cs[d0 + j], si = cs[half + d0 + j];
-      xo[j] = x.f(j) * co - y.f(j) * si;
-      yo[j] = y.f(j) * co + x.f(j) * si;
-    }
+    rope_rotate8(x, y, cs + d0, cs + half + d0, xo, yo);
     *reinterpret_cast<uint4*>(base + d0) = pack_bf16x8(xo);
     *reinterpret_cast<uint4*>(base + half + d0) = pack_bf16x8(yo);
   }
@@ -75,12 +70,7 @@ __global__ void rope_kv_kernel(
     bf16x8 x = load_bf16x8(base + d0);
     bf16x8 y = load_bf16x8(base + half + d0);
     float xo[8], yo[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float co = cs[d0 + j], si = cs[half + d0 + j];
-      xo[j] = x.f(j) * co - y.f(j) * si;
-      yo[j] = y.f(j) * co + x.f(j) * si;
-    }
+    rope_rotate8(x, y, cs + d0, cs + half + d0, xo, yo);
     uint4 px = pack_bf16x8(xo), py = pack_bf16x8(yo);
     *reinterpret_cast<uint4*>(base + d0) = px;
     *reinterpret_cast<uint4*>(base + half + d0) = py;

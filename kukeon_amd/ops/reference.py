@@ -129,6 +129,23 @@ def paged_attention(out: torch.Tensor, q: torch.Tensor, k_cache: torch.Tensor,
             out.view(B, Hq, D)[b, h] = o.to(out.dtype)
 
 
+def paged_attention_rope(out: torch.Tensor, qkv: torch.Tensor,
+                         k_cache: torch.Tensor, v_cache: torch.Tensor,
+                         cos_sin: torch.Tensor, positions: torch.Tensor,
+                         block_table: torch.Tensor, seq_lens: torch.Tensor,
+                         num_q_heads: int, num_kv_heads: int,
+                         num_splits: int, scale: float, tmp_out=None,
+                         tmp_ml=None) -> None:
+    """rope_kv_append (table mode) + paged_attention on a copy of `qkv`,
+    which the fused op leaves untouched."""
+    rot = qkv.clone()
+    rope_kv_append(rot, k_cache, v_cache, cos_sin, positions, None,
+                   num_q_heads, num_kv_heads, k_cache.shape[3],
+                   block_table=block_table)
+    paged_attention(out, rot, k_cache, v_cache, block_table, seq_lens, 0,
+                    num_splits, scale, tmp_out, tmp_ml)
+
+
 def prefill_attention(out: torch.Tensor, q: torch.Tensor,
                       k_cache: torch.Tensor, v_cache: torch.Tensor,
                       block_table: torch.Tensor, seq_lens: torch.Tensor,

@@ -1,54 +1,140 @@
-"""Micro-bench the decode paged-attention kernel at bench-like shapes and
-report achieved KV bandwidth vs the ~6.3 TB/s practical HBM3E roofline."""
+"""Micro-bench decode attention at bench-like shapes: the fused op
+(ops.paged_attention_rope, one launch when S <= 8) against the three-launch
+sequence rope_kv_append + paged_attention (attention + reduce), with the
+achieved KV bandwidth vs the ~6.3 TB/s practical HBM3E roofline.
+
+Same process, alternating, median of ROUNDS rounds. Each variant is a
+captured graph (as in serving) of one call per cache copy; the copies
+rotate so that every call streams KV the LLC no longer holds (enough
+copies to overflow a 256 MB LLC twice). Prints one JSON line per shape.
+
+  python scripts/bench_paged_attn.py [--kv-dtype fp8] [--batches 64,8,...]
+"""
+import argparse
+import json
+import statistics
 import sys
-import time
 
 import torch
 
 sys.path.insert(0, ".")
 import kukeon_amd.ops as ops  # noqa: E402
 
-
-def t(fn, n=50):
-    for _ in range(5):
-        fn()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(n):
-        fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) / n * 1e6
-
-
 DEV = "cuda:0"
-B, Hq, Hk, D, BS = 64, 32, 8, 128, 16
-torch.manual_seed(0)
-for ctx_lo, ctx_hi in [(512, 3584), (1500, 1500), (3584, 3584)]:
-    ctxs = torch.randint(ctx_lo, ctx_hi + 1, (B,)).tolist() \
-        if ctx_lo != ctx_hi else [ctx_lo] * B
+Hq, Hk, D, BS = 32, 8, 128, 16
+LLC_BYTES = 256 << 20
+ROUNDS = 7
+MAXPOS = 4096
+
+
+def engine_splits(B):
+    """LLMEngine._decode_splits for Hk kv heads."""
+    want = (16 * 256 + B * Hk - 1) // (B * Hk)
+    return max(4, min(32, ((want + 3) // 4) * 4))
+
+
+def make_graph(fn, n):
+    for i in range(n):          # warm up outside capture
+        fn(i)
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        for i in range(n):
+            fn(i)
+    return g
+
+
+def time_graph(g, n, reps):
+    """us per call of one replay train."""
+    e0 = torch.cuda.Event(enable_timing=True)
+    e1 = torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        g.replay()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) * 1e3 / (reps * n)
+
+
+def bench_shape(B, ctx_lo, ctx_hi, fp8, splits=None):
+    gen = torch.Generator().manual_seed(B * 7919 + ctx_lo)
+    ctxs = torch.randint(ctx_lo, ctx_hi + 1, (B,), generator=gen).tolist()
     nb = [(c + BS - 1) // BS for c in ctxs]
     NB = sum(nb) + 8
-    kc = torch.randn(NB, Hk, BS, D, dtype=torch.bfloat16, device=DEV)
-    vc = torch.randn(NB, Hk, BS, D, dtype=torch.bfloat16, device=DEV)
-    maxb = max(nb)
-    bt = torch.zeros(B, maxb, dtype=torch.int32, device=DEV)
+    esz = 1 if fp8 else 2
+    kv_bytes = sum(ctxs) * Hk * D * esz * 2
+    copies = max(2, -(-2 * LLC_BYTES // kv_bytes) + 1)
+
+    def cache():
+        x = torch.randn(NB, Hk, BS, D, dtype=torch.bfloat16, device=DEV)
+        if fp8:
+            x = x.float().to(torch.float8_e4m3fn).view(torch.uint8)
+        return x
+
+    kcs = [cache() for _ in range(copies)]
+    vcs = [cache() for _ in range(copies)]
+    bt = torch.zeros(B, max(nb), dtype=torch.int32, device=DEV)
     nxt = 0
     for b in range(B):
         bt[b, : nb[b]] = torch.arange(nxt, nxt + nb[b], dtype=torch.int32)
         nxt += nb[b]
     seq_lens = torch.tensor(ctxs, dtype=torch.int32, device=DEV)
-    q = torch.randn(B, Hq * D, dtype=torch.bfloat16, device=DEV)
+    pos = seq_lens - 1
+    slots = torch.zeros(B, dtype=torch.int32, device=DEV)
+    inv = 1.0 / (500000.0 ** (torch.arange(0, D, 2).float() / D))
+    fr = torch.outer(torch.arange(MAXPOS).float(), inv)
+    cos_sin = torch.cat([fr.cos(), fr.sin()], dim=1).to(DEV)
+    qkv = torch.randn(B, (Hq + 2 * Hk) * D, dtype=torch.bfloat16, device=DEV)
+    qkv_seq = qkv.clone()   # the sequence rotates its qkv in place
     out = torch.empty(B, Hq * D, dtype=torch.bfloat16, device=DEV)
     scale = D ** -0.5
-    kv_bytes = sum(ctxs) * Hk * D * 2 * 2
-    print(f"ctx {ctx_lo}-{ctx_hi} (KV {kv_bytes/1e6:.0f} MB/call):")
-    for splits in (4, 8, 16):
-        tmp_out = torch.zeros(B, Hq, splits, D, dtype=torch.float32,
-                              device=DEV)
-        tmp_ml = torch.zeros(B, Hq, splits, 2, dtype=torch.float32,
-                             device=DEV)
-        us = t(lambda: ops.paged_attention(out, q, kc, vc, bt, seq_lens, 0,
-                                           splits, scale, tmp_out, tmp_ml))
-        bw = kv_bytes / (us * 1e-6) / 1e12
-        print(f"  splits={splits:2d}:  {us:7.1f}us {bw:5.2f}TB/s"
-              f" ({bw/6.3*100:4.1f}%)", flush=True)
+    S = splits or engine_splits(B)
+    tmp_out = torch.zeros(B, Hq, S, D, dtype=torch.float32, device=DEV)
+    tmp_ml = torch.zeros(B, Hq, S, 2, dtype=torch.float32, device=DEV)
+
+    def fused(i):
+        ops.paged_attention_rope(out, qkv, kcs[i], vcs[i], cos_sin, pos, bt,
+                                 seq_lens, Hq, Hk, S, scale, tmp_out, tmp_ml)
+
+    def sequence(i):
+        ops.rope_kv_append(qkv_seq, kcs[i], vcs[i], cos_sin, pos, slots, Hq,
+                           Hk, D, block_table=bt)
+        ops.paged_attention(out, qkv_seq, kcs[i], vcs[i], bt, seq_lens, 0, S,
+                            scale, tmp_out, tmp_ml)
+
+    graphs = {"fused": make_graph(fused, copies),
+              "sequence": make_graph(sequence, copies)}
+    reps = max(2, 200 // copies)
+    times = {k: [] for k in graphs}
+    for _ in range(ROUNDS):
+        for k, g in graphs.items():     # alternating
+            times[k].append(time_graph(g, copies, reps))
+    res = {"B": B, "ctx": [ctx_lo, ctx_hi], "kv": "fp8" if fp8 else "bf16",
+           "splits": S, "kv_mb": round(kv_bytes / 1e6, 1), "copies": copies}
+    for k, ts in times.items():
+        med = statistics.median(ts)
+        res[k + "_us"] = round(med, 2)
+        res[k + "_spread_us"] = round(max(ts) - min(ts), 2)
+        res[k + "_tbps"] = round(kv_bytes / (med * 1e-6) / 1e12, 2)
+    res["sequence_over_fused"] = round(res["sequence_us"] / res["fused_us"], 3)
+    print(json.dumps(res), flush=True)
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--kv-dtype", default="bf16", choices=("bf16", "fp8"))
+    ap.add_argument("--batches", default="64,8,16,32,128,256")
+    args = ap.parse_args()
+    fp8 = args.kv_dtype == "fp8"
+    for B in (int(b) for b in args.batches.split(",")):
+        # the serving mix, and at the headline batch also uniform contexts
+        shapes = [(512, 3584)]
+        if B == 64:
+            shapes += [(1500, 1500), (3584, 3584)]
+        for lo, hi in shapes:
+            bench_shape(B, lo, hi, fp8)
+
+
+if __name__ == "__main__":
+    main()
