@@ -4,7 +4,8 @@ Design (MI355X-first, not a port — the reference eminwux/kukeon has no
 inference plane at all):
 
 * one engine per GPU process; sessions own persistent KV (multi-turn agent
-  context stays resident in the 288 GB HBM across turns),
+  context stays resident in the 288 GB HBM across turns); sessions forked
+  from a common context share its full KV blocks by reference count,
 * prefill runs as a packed varlen batch (GEMM-bound at 32k tokens),
 * decode runs the whole running set each step; the full forward + logits +
   top-k/top-p sampling is captured in a hipGraph per batch-size bucket so a
@@ -160,6 +161,10 @@ class LLMEngine:
     # ------------------------------------------------------------------
     def add_request(self, kv: SequenceKV, prompt_tokens: List[int],
                     sampling: SamplingParams) -> int:
+        evicted = kv.num_tokens == 0 and bool(kv.history)
+        if (sampling.max_new_tokens == 0 and not prompt_tokens
+                and kv.pending_token is None and not evicted):
+            raise ValueError("prefill-only request with nothing to prefill")
         rid = self._next_id
         self._next_id += 1
         self._known_kvs[id(kv)] = kv
@@ -185,6 +190,55 @@ class LLMEngine:
         kv.num_tokens = 0
         kv.pending_token = None
         kv.history = []
+
+    def fork_sequence(self, src: SequenceKV, n: int = 1) -> List[SequenceKV]:
+        """Fork `n` children that start from `src`'s context without
+        prefilling it again: they share its full blocks and each get a copy
+        of its partially filled tail block (one kv_copy_blocks launch for
+        the whole call, enqueued on the current stream before returning).
+        `src` must have no active request — its tail is being written
+        otherwise. MemoryError (pool cannot supply the tail blocks) leaves
+        every reference count as it was. An evicted source forks to
+        children that carry only its history and re-prefill like it.
+
+        Sharing is safe without copy-on-write because shared blocks are
+        immutable: only blocks wholly below num_tokens are shared, that
+        holds for every holder (a child starts at the parent's num_tokens
+        and both only grow), and nothing in the engine writes below
+        num_tokens — prefill append, the fused decode kernel and the
+        stop-token rollback all act at or above it. The block a session
+        appends to is therefore always its own."""
+        if n < 1:
+            raise ValueError("fork_sequence needs n >= 1")
+        if any(r.kv is src for r in self.waiting) or \
+                any(r is not None and r.kv is src for r in self._rows):
+            raise ValueError("cannot fork a session with an active request")
+        bs = self.ecfg.block_size
+        full, tail = divmod(src.num_tokens, bs)
+        alloc = self.kv.allocator
+        # first, and the only step that can fail: nothing to undo
+        tails = alloc.alloc(n) if tail else []
+        shared = src.blocks[:full]
+        children = []
+        for i in range(n):
+            alloc.share(shared)
+            kv = SequenceKV(bs)
+            # surplus blocks src reserved beyond its context stay its own
+            kv.blocks = shared + tails[i:i + 1]
+            kv.num_tokens = src.num_tokens
+            kv.history = list(src.history)
+            kv.pending_token = src.pending_token
+            self._known_kvs[id(kv)] = kv
+            children.append(kv)
+        if tails:
+            assert src.blocks[full] not in tails
+            dev = self.device
+            ops.kv_copy_blocks(
+                self.kv.k, self.kv.v,
+                torch.tensor([src.blocks[full]] * n, dtype=torch.int32,
+                             device=dev),
+                torch.tensor(tails, dtype=torch.int32, device=dev))
+        return children
 
     def has_work(self) -> bool:
         return bool(self.waiting) or self.num_running > 0
@@ -245,16 +299,21 @@ class LLMEngine:
         this, resident-but-idle context starves new admissions forever."""
         active = {id(r.kv) for r in self.waiting}
         active.update(id(r.kv) for r in self._rows if r is not None)
-        victim = None
+        # rank by what the eviction returns to the pool: blocks shared with
+        # a forked session only lose a reference. A session that returns
+        # none stays a candidate, last — dropping its references is what
+        # later makes the co-owner's blocks releasable.
+        victim, gain = None, -1
         for kv in self._known_kvs.values():
             if id(kv) in active or not kv.blocks:
                 continue
-            if victim is None or len(kv.blocks) > len(victim.blocks):
-                victim = kv
+            g = self.kv.allocator.num_exclusive(kv.blocks)
+            if g > gain:
+                victim, gain = kv, g
         if victim is None:
             return False
-        log.info("evicting idle session KV (%d blocks) to unblock admission",
-                 len(victim.blocks))
+        log.info("evicting idle session KV (%d blocks, %d to the pool) to "
+                 "unblock admission", len(victim.blocks), gain)
         self.kv.allocator.free(victim.blocks)
         victim.blocks = []
         victim.num_tokens = 0
@@ -278,8 +337,12 @@ class LLMEngine:
         # sessions x 257 tokens vs a 16384 budget the hard cutoff cost an
         # entire 64-token full-layer sweep (~a decode step) per turn.
         slack = budget // 16
-        while self.waiting and avail_rows > 0 and tokens < budget:
+        while self.waiting and tokens < budget:
             req = self.waiting[0]
+            # a prefill-only request (max_new_tokens == 0) takes no row
+            wants_row = req.sampling.max_new_tokens > 0
+            if wants_row and avail_rows <= 0:
+                break
             remaining = len(req.prompt_tokens) - req.prefill_pos
             chunk = min(remaining, budget - tokens)
             if 0 < remaining - chunk <= slack and tokens + remaining <= \
@@ -297,7 +360,7 @@ class LLMEngine:
             free -= need
             tokens += chunk
             if finishing:
-                avail_rows -= 1
+                avail_rows -= wants_row
                 batch.append((self.waiting.pop(0), chunk))
             else:
                 batch.append((req, chunk))
@@ -352,21 +415,27 @@ class LLMEngine:
                         qb_start=torch.tensor(qb_start, dtype=torch.int32,
                                               device=dev))
         hidden = self.model.forward(t_ids, self.kv.k, self.kv.v, meta)
-        # sample only the requests whose prompt completed this pass
-        finishing = [(i, r) for i, (r, _) in enumerate(batch)
-                     if r.prefill_pos == len(r.prompt_tokens)]
-        if not finishing:
-            return []
-        last_rows, acc = [], 0
-        for i, (r, chunk) in enumerate(batch):
+        # sample only the requests whose prompt completed this pass; a
+        # prefill-only one (max_new_tokens == 0) ends here with no token,
+        # no row and nothing pending
+        outs, sampled, last_rows, acc = [], [], [], 0
+        for r, chunk in batch:
             acc += chunk
-            if r.prefill_pos == len(r.prompt_tokens):
+            if r.prefill_pos != len(r.prompt_tokens):
+                continue
+            if r.sampling.max_new_tokens == 0:
+                r.finished = True
+                outs.append(StepOutput(r.req_id, [], True))
+            else:
+                sampled.append(r)
                 last_rows.append(acc - 1)
+        if not sampled:
+            return outs
         logits = self.model.compute_logits(
             hidden[torch.tensor(last_rows, dtype=torch.long, device=dev)])
-        toks = self._sample_eager([r for _, r in finishing], logits)
-        return [self._append_token(r, t)
-                for (_, r), t in zip(finishing, toks)]
+        toks = self._sample_eager(sampled, logits)
+        return outs + [self._append_token(r, t)
+                       for r, t in zip(sampled, toks)]
 
     def _sample_eager(self, reqs: List[Request], logits: torch.Tensor):
         B = len(reqs)

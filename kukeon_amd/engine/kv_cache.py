@@ -15,15 +15,27 @@ import torch
 
 
 class BlockAllocator:
-    """Free-list block allocator (exact, O(1) alloc/free)."""
+    """Free-list block allocator with a reference count per block.
+
+    alloc hands a block out at count 1, share adds a holder, free drops one
+    and returns the block to the free list only at zero — so sessions forked
+    from a common prefix hold the same blocks. Without share it is the plain
+    free list: same blocks in the same order (exact, O(1) per block)."""
 
     def __init__(self, num_blocks: int):
         self.num_blocks = num_blocks
         self._free: List[int] = list(range(num_blocks - 1, -1, -1))
+        self._refs: List[int] = [0] * num_blocks
+        self._num_shared = 0
 
     @property
     def num_free(self) -> int:
         return len(self._free)
+
+    @property
+    def num_shared(self) -> int:
+        """Blocks held by more than one sequence."""
+        return self._num_shared
 
     def alloc(self, n: int) -> List[int]:
         if n > len(self._free):
@@ -31,10 +43,37 @@ class BlockAllocator:
                 f"KV cache exhausted: want {n} blocks, {len(self._free)} free")
         out = self._free[-n:][::-1]
         del self._free[-n:]
+        for b in out:
+            self._refs[b] = 1
         return out
 
+    def share(self, blocks: List[int]) -> None:
+        """Add one reference to each (allocated) block."""
+        refs = self._refs
+        for b in blocks:
+            if refs[b] <= 0:
+                raise ValueError(f"share of free KV block {b}")
+        for b in blocks:
+            refs[b] += 1
+            if refs[b] == 2:
+                self._num_shared += 1
+
     def free(self, blocks: List[int]) -> None:
-        self._free.extend(reversed(blocks))
+        """Drop one reference from each block."""
+        refs = self._refs
+        for b in reversed(blocks):
+            if refs[b] <= 0:
+                raise ValueError(f"double free of KV block {b}")
+            refs[b] -= 1
+            if refs[b] == 0:
+                self._free.append(b)
+            elif refs[b] == 1:
+                self._num_shared -= 1
+
+    def num_exclusive(self, blocks: List[int]) -> int:
+        """How many of `blocks` a free() of them would return to the pool."""
+        refs = self._refs
+        return sum(1 for b in blocks if refs[b] == 1)
 
 
 class SequenceKV:

@@ -73,6 +73,16 @@ def rope_kv_append(qkv, k_cache, v_cache, cos_sin, positions, slot_mapping,
                               head_dim, block_table)
 
 
+def kv_copy_blocks(k_cache, v_cache, src, dst) -> None:
+    """cache[l, dst[i]] = cache[l, src[i]] for every layer l, every pair i
+    and both caches [L, NB, Hk, BS, D], as raw bytes (bf16 and fp8 caches
+    alike) in one launch; an empty pair list launches nothing. `src` and
+    `dst` are int32 tensors of equal length on the caches' device. A source
+    may repeat; destinations must be distinct and disjoint from the
+    sources, which the caller guarantees."""
+    _impl(k_cache).kv_copy_blocks(k_cache, v_cache, src, dst)
+
+
 def decode_advance(ids, pos, seq_lens, tokens, ring, counter) -> None:
     _impl(ids).decode_advance(ids, pos, seq_lens, tokens, ring, counter)
 

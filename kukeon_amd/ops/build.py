@@ -22,6 +22,7 @@ SOURCES = [
     "rmsnorm.hip",
     "activation.hip",
     "rope_kv.hip",
+    "kv_copy.hip",
     "paged_attn.hip",
     "prefill_attn.hip",
     "mfma_probe.hip",

@@ -15,6 +15,8 @@ void rope_kv_append(torch::Tensor qkv, torch::Tensor k_cache,
 void decode_advance(torch::Tensor ids, torch::Tensor pos,
                     torch::Tensor seq_lens, torch::Tensor tokens,
                     torch::Tensor ring, torch::Tensor counter);
+void kv_copy_blocks(torch::Tensor k_cache, torch::Tensor v_cache,
+                    torch::Tensor src, torch::Tensor dst);
 void paged_attention(torch::Tensor out, torch::Tensor q, torch::Tensor k_cache,
                      torch::Tensor v_cache, torch::Tensor block_table,
                      torch::Tensor seq_lens, int64_t q_offset,
@@ -93,6 +95,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("silu_mul", &kukeon::silu_mul, "out = silu(gate)*up from fused [T,2I]");
   m.def("rope_kv_append", &kukeon::rope_kv_append,
         "in-place NEOX RoPE on fused qkv + paged KV append");
+  m.def("kv_copy_blocks", &kukeon::kv_copy_blocks,
+        "cache[l, dst[i]] = cache[l, src[i]] for K and V, all layers, one "
+        "launch");
   m.def("paged_attention", &kukeon::paged_attention,
         "decode paged attention (GQA, split-KV)");
   m.def("paged_attention_rope", &kukeon::paged_attention_rope,

@@ -88,6 +88,16 @@ def rope_kv_append(qkv: torch.Tensor, k_cache: torch.Tensor,
         v_cache[blk, :, off] = v[t]
 
 
+def kv_copy_blocks(k_cache: torch.Tensor, v_cache: torch.Tensor,
+                   src: torch.Tensor, dst: torch.Tensor) -> None:
+    """cache[:, dst] = cache[:, src] on [L, NB, Hk, BS, D] caches."""
+    assert k_cache.shape == v_cache.shape and src.shape == dst.shape
+    if src.numel() == 0:
+        return
+    k_cache[:, dst.long()] = k_cache[:, src.long()]
+    v_cache[:, dst.long()] = v_cache[:, src.long()]
+
+
 def _gather_kv(cache: torch.Tensor, block_table: torch.Tensor, ctx: int,
                b: int) -> torch.Tensor:
     """-> [ctx, Hk, D] from paged cache [NB, Hk, BS, D] (bf16 or fp8)."""

@@ -13,7 +13,10 @@ interleave across clients — the engine continuously batches them):
   -> {"id": N, "result": {"tokens": [...], "context_len": M}}
   other methods: ping, stats (KV occupancy + turn-latency
   percentiles), cancel (abort a session's in-flight turn), release
-  (free a session's KV). Passing
+  (free a session's KV), fork ({"session", "new_sessions": [names]}:
+  new sessions that share the source's KV prefix blocks instead of
+  prefilling its context again). "max_new_tokens": 0 on generate only
+  prefills the tokens (a template to fork from). Passing
   "stream": true on generate delivers incremental
   {"id": N, "delta": [tok, ...]} frames (one per decode micro-batch)
   ahead of the final result frame — time-to-first-token for agents.
@@ -190,6 +193,7 @@ class ModelhubServer:
                 "waiting": len(self.engine.waiting),
                 "kv_blocks_total": kv.num_blocks,
                 "kv_blocks_free": kv.allocator.num_free,
+                "kv_blocks_shared": kv.allocator.num_shared,
                 "weight_dtype": getattr(self.engine.model, "weight_dtype",
                                         "bf16"),
                 "weight_bytes": _resident_weight_bytes(self.engine.model),
@@ -240,6 +244,38 @@ class ModelhubServer:
                 self.engine.free_sequence(kv)
                 done.put({})
             self._submit.put(_do_release)
+            out = done.get(timeout=60)
+            if "error" in out:
+                raise ValueError(out["error"])
+            return out
+        if method == "fork":
+            name = params["session"]
+            new_names = list(params["new_sessions"])
+            done: "queue.Queue" = queue.Queue()
+
+            def _do_fork():
+                kv = self.sessions.get(name)
+                taken = [s for s in new_names if s in self.sessions]
+                if kv is None:
+                    done.put({"error": f"unknown session {name}"})
+                elif not new_names or taken or \
+                        len(set(new_names)) != len(new_names):
+                    done.put({"error": "new_sessions must be new, distinct "
+                                       f"names (already present: {taken})"})
+                else:
+                    try:
+                        # refuses a source with a request in flight
+                        kids = self.engine.fork_sequence(kv, len(new_names))
+                    except (ValueError, MemoryError) as e:
+                        done.put({"error": f"fork of {name} failed: {e}"})
+                        return
+                    self.sessions.update(zip(new_names, kids))
+                    shared = kv.num_tokens // kv.block_size
+                    done.put({"context_len": kv.num_tokens,
+                              "shared_blocks": shared,
+                              "copied_blocks": sum(len(c.blocks) - shared
+                                                   for c in kids)})
+            self._submit.put(_do_fork)
             out = done.get(timeout=60)
             if "error" in out:
                 raise ValueError(out["error"])
@@ -390,6 +426,12 @@ class ModelhubClient:
 
     def generate(self, session: str, tokens: List[int], **kw):
         return self.call("generate", session=session, tokens=tokens, **kw)
+
+    def fork(self, session: str, new_sessions: List[str]):
+        """Create `new_sessions` from `session`'s context, sharing its KV
+        prefix blocks; -> {"context_len", "shared_blocks",
+        "copied_blocks"}."""
+        return self.call("fork", session=session, new_sessions=new_sessions)
 
     def generate_stream(self, session: str, tokens: List[int], **kw):
         """Yield token deltas as the engine produces them; the final
