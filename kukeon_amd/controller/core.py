@@ -1607,7 +1607,9 @@ class Controller:
                                 gpus: int = 1, socket_path: str = "",
                                 extra_args: Optional[List[str]] = None,
                                 start: bool = True,
-                                weight_dtype: str = "") -> api.CellDoc:
+                                weight_dtype: str = "",
+                                shared_prefix_min_tokens: Optional[int] = None
+                                ) -> api.CellDoc:
         """Provision the inference server as a system-realm cell (the same
         pattern the reference uses for kukeond itself)."""
         import sys as _sys
@@ -1620,6 +1622,9 @@ class Controller:
                 "--socket", sock] + list(extra_args or [])
         if weight_dtype:
             args += ["--weight-dtype", weight_dtype]
+        if shared_prefix_min_tokens is not None:
+            args += ["--shared-prefix-min-tokens",
+                     str(shared_prefix_min_tokens)]
         doc = api.CellDoc(
             metadata=api.Metadata(name="modelhub"),
             spec=api.CellSpec(

@@ -76,6 +76,13 @@ MODEL_PRESETS = {
 }
 
 
+# the smallest swept prefix (512 / 1024 / 2048 / 3072 tokens) at which the
+# shared path beat the unshared op by more than both spreads in every
+# measured configuration (GQA group 4 and 8, bf16 and fp8 cache); at 1024
+# only group 4 did (docs/perf.md)
+SHARED_PREFIX_MIN_TOKENS_DEFAULT = 2048
+
+
 @dataclass
 class EngineConfig:
     block_size: int = 16
@@ -94,6 +101,11 @@ class EngineConfig:
                                     # the KV bandwidth, 2x the capacity)
     seed: int = 1234
     tp_size: int = 1
+    # decode attention reads the KV blocks that forked sessions share once
+    # per tile of sessions when the common prefix has at least this many
+    # tokens (ops.paged_attention_shared); 0 = never. docs/perf.md has the
+    # measurement behind the default.
+    shared_prefix_min_tokens: int = SHARED_PREFIX_MIN_TOKENS_DEFAULT
 
     @property
     def max_blocks_per_seq(self) -> int:

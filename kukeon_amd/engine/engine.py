@@ -158,6 +158,29 @@ class LLMEngine:
         self.graphs: Dict[int, torch.cuda.CUDAGraph] = {}
         self._graph_pool = None
 
+        # ---- shared-prefix decode (see _regroup) ----
+        # graphs of the shared path, by bucket, apart from self.graphs
+        self.shared_graphs: Dict[int, torch.cuda.CUDAGraph] = {}
+        self.tile_width = 16 // max(1, self.hq // self.hk)
+        max_tiles = max(1, self.Bmax // 2)
+        self.h_prefix_blocks = torch.zeros(self.Bmax, dtype=torch.int32,
+                                           pin_memory=pin)
+        self.h_tiles = torch.zeros(max_tiles, 2 + 16, dtype=torch.int32,
+                                   pin_memory=pin)
+        self.d_prefix_blocks = torch.zeros(self.Bmax, dtype=torch.int32,
+                                           device=d)
+        self.d_tiles = torch.zeros(max_tiles, 2 + 16, dtype=torch.int32,
+                                   device=d)
+        self.n_prefix_blocks = self.h_prefix_blocks.numpy()
+        self.n_tiles = self.h_tiles.numpy()
+        self._groups_dirty = False      # row membership changed
+        self._num_tiles = 0             # tiles in use after the last regroup
+        self._tile_rows = 0             # rows in them
+        # decode steps that took the shared path, and the rows that were
+        # in tiles at the last decode step (0 if it was an unshared one)
+        self.shared_prefix_steps = 0
+        self.shared_prefix_rows = 0
+
     # ------------------------------------------------------------------
     def add_request(self, kv: SequenceKV, prompt_tokens: List[int],
                     sampling: SamplingParams) -> int:
@@ -462,9 +485,12 @@ class LLMEngine:
         self.h_params[row, 1] = float(req.sampling.top_k)
         self.h_params[row, 2] = req.sampling.top_p
         self._params_dirty = True
+        self._groups_dirty = True
 
     def _release_row(self, req: Request) -> None:
         if req.row >= 0:
+            # also how _preempt and cancel take a row out of its group
+            self._groups_dirty = True
             self._rows[req.row] = None
             self._free_rows.append(req.row)
             self.n_slots[req.row] = -1
@@ -523,6 +549,81 @@ class LLMEngine:
         # kernel. A multiple of 4 keeps every workgroup's waves busy.
         want = (16 * 256 + bucket * self.hk - 1) // (bucket * self.hk)
         return max(4, min(self.max_splits, ((want + 3) // 4) * 4))
+
+    def _prefix_splits(self, bucket: int) -> int:
+        # the prefix kernel runs tiles * Hk * prefix_splits waves; a bucket
+        # whose rows are all grouped has bucket / tile_width tiles. Unlike
+        # a suffix split, a prefix split costs every member row a
+        # workspace slot that the reduce kernel reads back, so that case
+        # is given a quarter of the 4096 waves of _decode_splits, but at
+        # least 8 splits, as a multiple of 4 for the 4-wave workgroups
+        # and capped like the suffix's: 8 at bucket 64 for both the 8B
+        # (16 tiles) and the 70B shape (32 tiles), where 8 measured
+        # fastest of 4 / 8 / 16 / 32 (docs/perf.md). The graph of a bucket
+        # is captured once, so the count cannot follow the tiles in use.
+        tiles = max(1, bucket // max(1, self.tile_width))
+        want = (4 * 256 + tiles * self.hk - 1) // (tiles * self.hk)
+        return max(8, min(self.max_splits, ((want + 3) // 4) * 4))
+
+    def _regroup(self) -> None:
+        """Recompute the shared-prefix tiles of the running rows into the
+        host staging buffers. Rows whose block lists begin with the same
+        block id form a group (forks of one context; nested forks are not
+        told apart: the group shares the prefix common to ALL rows with
+        that first block, and a sub-family's longer common run is read per
+        row). Its prefix is the longest run of block ids common to every
+        member among the blocks wholly below every member's num_tokens. A
+        group is used when it has at least 2 rows and at least
+        shared_prefix_min_tokens tokens of prefix; it is cut into tiles of
+        tile_width = 16 // (Hq // Hk) rows, and a lone leftover row stays
+        ungrouped (alone it gains nothing), so there are never more than
+        rows // 2 tiles. With tile_width 1 (GQA group of 16) nothing can
+        share and the path stays off.
+
+        Block lists only grow and shared blocks are immutable (see
+        fork_sequence), so a prefix stays valid until row membership
+        changes: _assign_row and _release_row (hence _preempt, cancel and a
+        finished request) mark the groups dirty, and the next decode step
+        calls this once."""
+        self._groups_dirty = False
+        bs = self.ecfg.block_size
+        min_tokens = self.ecfg.shared_prefix_min_tokens
+        W = self.tile_width
+        tiles = []
+        if min_tokens > 0 and W >= 2:
+            by_first: Dict[int, List[int]] = {}
+            for row, r in enumerate(self._rows):
+                if r is not None and r.kv.blocks:
+                    by_first.setdefault(r.kv.blocks[0], []).append(row)
+            for rows in by_first.values():
+                if len(rows) < 2:
+                    continue
+                kvs = [self._rows[row].kv for row in rows]
+                limit = min(kv.num_tokens // bs for kv in kvs)
+                first = kvs[0].blocks
+                p = 0
+                while p < limit and all(kv.blocks[p] == first[p]
+                                        for kv in kvs[1:]):
+                    p += 1
+                if p == 0 or p * bs < min_tokens:
+                    continue
+                for i in range(0, len(rows), W):
+                    if len(rows) - i >= 2:
+                        tiles.append((p, rows[i:i + W]))
+        self.n_prefix_blocks[:] = 0
+        self.n_tiles[:] = 0
+        for t, (p, rows) in enumerate(tiles):
+            self.n_tiles[t, 0] = len(rows)
+            self.n_tiles[t, 1] = p
+            self.n_tiles[t, 2:2 + len(rows)] = rows
+            self.n_prefix_blocks[rows] = p
+        self._num_tiles = len(tiles)
+        self._tile_rows = sum(len(rows) for _, rows in tiles)
+        if tiles:
+            ops.check_prefix_tiles(self.h_tiles[:len(tiles)],
+                                   max(1, self.hq // self.hk))
+        self.d_prefix_blocks.copy_(self.h_prefix_blocks, non_blocking=True)
+        self.d_tiles.copy_(self.h_tiles, non_blocking=True)
 
     def _tmp_for(self, bucket: int, splits: int):
         key = (bucket, splits)
@@ -619,19 +720,28 @@ class LLMEngine:
             self.d_topp.copy_(self.h_params[:, 2], non_blocking=True)
             self._params_dirty = False
         self.d_step.zero_()
-        if use_graph and bucket not in self.graphs:
+        # the shared-prefix path: taken when at least one group qualifies;
+        # tiles and prefix lengths are staged only when membership changed
+        enabled = self.ecfg.shared_prefix_min_tokens > 0
+        if enabled and self._groups_dirty:
+            self._regroup()
+        shared = enabled and self._num_tiles > 0
+        graphs = self.shared_graphs if shared else self.graphs
+        if use_graph and bucket not in graphs:
             # capture AFTER the staging copies: the warmup forward then runs
             # on the real current state (its KV writes land exactly where
             # the first replay re-writes the same values), never on stale
             # block tables pointing at freed blocks.
-            self._capture_safely(bucket)
+            self._capture_safely(bucket, shared)
         if use_graph:
-            g = self.graphs[bucket]
+            g = graphs[bucket]
             for _ in range(k):
                 g.replay()
         else:
             for _ in range(k):
-                self._decode_forward(bucket)
+                self._decode_forward(bucket, shared)
+        self.shared_prefix_steps += k if shared else 0
+        self.shared_prefix_rows = self._tile_rows if shared else 0
         slab = self.d_ring[: k * bucket].view(k, bucket)[:, :nrows].cpu()
         outs = []
         for row, r in active:
@@ -659,14 +769,28 @@ class LLMEngine:
             outs.append(StepOutput(r.req_id, emitted, fin))
         return outs
 
-    def _decode_forward(self, B: int) -> None:
+    def _decode_forward(self, B: int, shared: bool = False) -> None:
         splits = self._decode_splits(B)
-        tmp_out, tmp_ml = self._tmp_for(B, splits)
-        meta = AttnMeta(
-            mode="decode", positions=self.d_pos[:B],
-            slot_mapping=self.d_slots[:B], block_table=self.d_bt[:B],
-            seq_lens=self.d_seq_lens[:B], num_splits=splits,
-            tmp_out=tmp_out, tmp_ml=tmp_ml)
+        if shared:
+            # B // 2 tiles is the most _regroup can make of B rows; the
+            # workspaces grow by the prefix slots for this path only
+            psplits = self._prefix_splits(B)
+            tmp_out, tmp_ml = self._tmp_for(B, psplits + splits)
+            meta = AttnMeta(
+                mode="decode", positions=self.d_pos[:B],
+                slot_mapping=self.d_slots[:B], block_table=self.d_bt[:B],
+                seq_lens=self.d_seq_lens[:B], num_splits=splits,
+                tmp_out=tmp_out, tmp_ml=tmp_ml,
+                prefix_blocks=self.d_prefix_blocks[:B],
+                prefix_tiles=self.d_tiles[:max(1, B // 2)],
+                prefix_splits=psplits)
+        else:
+            tmp_out, tmp_ml = self._tmp_for(B, splits)
+            meta = AttnMeta(
+                mode="decode", positions=self.d_pos[:B],
+                slot_mapping=self.d_slots[:B], block_table=self.d_bt[:B],
+                seq_lens=self.d_seq_lens[:B], num_splits=splits,
+                tmp_out=tmp_out, tmp_ml=tmp_ml)
         hidden = self.model.forward(self.d_ids[:B], self.kv.k, self.kv.v, meta)
         logits = self.model.compute_logits(hidden)
         ops.sample(self.d_tokens[:B], logits, self.d_temps[:B],
@@ -676,12 +800,12 @@ class LLMEngine:
                            self.d_seq_lens[:B], self.d_tokens[:B],
                            self.d_ring, self.d_step)
 
-    def _capture_safely(self, bucket: int) -> None:
+    def _capture_safely(self, bucket: int, shared: bool = False) -> None:
         """Capture a bucket graph mid-serving: the warmup forward mutates
         the self-advancing cursors, so snapshot and restore them."""
         saved = (self.d_ids.clone(), self.d_pos.clone(),
                  self.d_seq_lens.clone(), self.d_step.clone())
-        self._capture(bucket)
+        self._capture(bucket, shared)
         self.d_ids.copy_(saved[0])
         self.d_pos.copy_(saved[1])
         self.d_seq_lens.copy_(saved[2])
@@ -689,17 +813,19 @@ class LLMEngine:
         if self.is_cuda:
             torch.cuda.synchronize()
 
-    def _capture(self, bucket: int) -> None:
-        log.info("capturing decode graph for bucket %d", bucket)
+    def _capture(self, bucket: int, shared: bool = False) -> None:
+        log.info("capturing %sdecode graph for bucket %d",
+                 "shared-prefix " if shared else "", bucket)
         torch.cuda.synchronize()
-        self._decode_forward(bucket)  # warm up allocator + BLAS heuristics
+        # warm up allocator + BLAS heuristics
+        self._decode_forward(bucket, shared)
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g, pool=self._graph_pool):
-            self._decode_forward(bucket)
+            self._decode_forward(bucket, shared)
         if self._graph_pool is None:
             self._graph_pool = g.pool()
-        self.graphs[bucket] = g
+        (self.shared_graphs if shared else self.graphs)[bucket] = g
         torch.cuda.synchronize()
 
     def capture_all(self) -> None:

@@ -35,6 +35,11 @@ class AttnMeta:
     num_splits: int = 1
     tmp_out: Optional[torch.Tensor] = None    # decode split-KV workspaces
     tmp_ml: Optional[torch.Tensor] = None
+    # shared-prefix decode (ops.paged_attention_shared): all three or none.
+    # With them set the workspaces hold prefix_splits + num_splits slots.
+    prefix_blocks: Optional[torch.Tensor] = None   # [nseq] int32
+    prefix_tiles: Optional[torch.Tensor] = None    # [T, 2 + 16] int32
+    prefix_splits: int = 0
 
 
 def split_prefill_meta(meta: AttnMeta, parts: int = 2):
@@ -136,6 +141,25 @@ class LlamaAttention(nn.Module):
         # is bound by the fp8 -> bf16 conversions and the fused variant of
         # it measured 1-7% behind the sequence in most buckets
         # (docs/perf.md); paged_attention still merges in the workgroup
+        if meta.mode == "decode" and meta.prefix_tiles is not None:
+            # forked sessions: the shared prefix is attended to per tile of
+            # sibling rows; same bf16 / fp8 dispatch rule as below
+            if ops.DECODE_ATTN_FUSED and kc.dtype != torch.uint8:
+                ops.paged_attention_rope_shared(
+                    out, qkv, kc, vc, cos_sin, meta.positions,
+                    meta.block_table, meta.seq_lens, self.hq, self.hk,
+                    meta.num_splits, self.scale, meta.tmp_out, meta.tmp_ml,
+                    meta.prefix_blocks, meta.prefix_tiles,
+                    meta.prefix_splits)
+                return out
+            ops.rope_kv_append(qkv, kc, vc, cos_sin, meta.positions,
+                               meta.slot_mapping, self.hq, self.hk, self.d,
+                               block_table=meta.block_table)
+            ops.paged_attention_shared(
+                out, qkv, kc, vc, meta.block_table, meta.seq_lens, 0,
+                meta.num_splits, self.scale, meta.tmp_out, meta.tmp_ml,
+                meta.prefix_blocks, meta.prefix_tiles, meta.prefix_splits)
+            return out
         if (meta.mode == "decode" and ops.DECODE_ATTN_FUSED
                 and kc.dtype != torch.uint8):
             ops.paged_attention_rope(out, qkv, kc, vc, cos_sin,

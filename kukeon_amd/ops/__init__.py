@@ -125,6 +125,63 @@ def paged_attention_rope(out, qkv, k_cache, v_cache, cos_sin, positions,
                                     scale, tmp_out, tmp_ml)
 
 
+def check_prefix_tiles(tiles, group: int) -> None:
+    """Raise ValueError unless the host tensor `tiles` is int32 [T, 2 + 16]
+    with n_rows <= 16 // group in every tile. The shared ops cannot check
+    this themselves without reading device memory; whoever fills the tiles
+    on the host calls this before uploading them."""
+    reference.check_prefix_tiles(tiles, group)
+
+
+def paged_attention_shared(out, q, k_cache, v_cache, block_table, seq_lens,
+                           q_offset: int, num_splits: int, scale: float,
+                           tmp_out, tmp_ml, prefix_blocks, tiles,
+                           prefix_splits: int) -> None:
+    """paged_attention for rows that share leading cache blocks (forked
+    sessions): a tile of up to W = 16 // (Hq // Hk) sibling rows rides the
+    matrix cores' N axis together, so their common prefix blocks are
+    fetched and scored once per tile, not once per row.
+
+    `prefix_blocks` int32 [B]: how many leading blocks of row b a tile
+    covers, 0 for a row in no tile. `tiles` int32 [T, 2 + 16]: n_rows,
+    n_prefix_blocks, then the member rows; n_rows == 0 is an empty tile.
+    The prefix block ids are read from the first member's block table.
+    The caller guarantees that every member's table begins with those
+    n_prefix_blocks ids, that prefix_blocks[row] == n_prefix_blocks for
+    every member, that n_prefix_blocks * 16 <= the row's newest position
+    (the prefix is full, immutable blocks only), that a row is in at most
+    one tile, that members have seq_len > 0 and that n_rows <= W
+    (check_prefix_tiles). The CPU reference checks all of it; the GPU op
+    reads none of it on the host and clamps what it reads on the device to
+    the buffers' bounds.
+
+    The prefix is split `prefix_splits` ways and the rest of each row
+    `num_splits` ways, all merged by the reduce kernel: the workspaces hold
+    at least B*Hq*(prefix_splits + num_splits) slots of 128 and 2 floats.
+    `out` is paged_attention's up to summation order."""
+    _impl(q).paged_attention_shared(out, q, k_cache, v_cache, block_table,
+                                    seq_lens, q_offset, num_splits, scale,
+                                    tmp_out, tmp_ml, prefix_blocks, tiles,
+                                    prefix_splits)
+
+
+def paged_attention_rope_shared(out, qkv, k_cache, v_cache, cos_sin,
+                                positions, block_table, seq_lens,
+                                num_q_heads: int, num_kv_heads: int,
+                                num_splits: int, scale: float, tmp_out,
+                                tmp_ml, prefix_blocks, tiles,
+                                prefix_splits: int) -> None:
+    """paged_attention_rope with the metadata and workspaces of
+    paged_attention_shared. The caches come out bit-equal to
+    paged_attention_rope's (the append is the suffix pass's, unchanged) and
+    `qkv` is left untouched; n_prefix_blocks * 16 <= positions[row] keeps
+    the token being appended out of the prefix."""
+    _impl(qkv).paged_attention_rope_shared(
+        out, qkv, k_cache, v_cache, cos_sin, positions, block_table,
+        seq_lens, num_q_heads, num_kv_heads, num_splits, scale, tmp_out,
+        tmp_ml, prefix_blocks, tiles, prefix_splits)
+
+
 def prefill_attention(out, q, k_cache, v_cache, block_table, seq_lens,
                       q_starts, qb_seq, qb_start, q_offset: int,
                       scale: float) -> None:

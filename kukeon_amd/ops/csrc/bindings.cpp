@@ -29,6 +29,20 @@ void paged_attention_rope(torch::Tensor out, torch::Tensor qkv,
                           int64_t num_q_heads, int64_t num_kv_heads,
                           int64_t num_splits, double scale,
                           torch::Tensor tmp_out, torch::Tensor tmp_ml);
+void paged_attention_shared(torch::Tensor out, torch::Tensor q,
+                            torch::Tensor k_cache, torch::Tensor v_cache,
+                            torch::Tensor block_table, torch::Tensor seq_lens,
+                            int64_t q_offset, int64_t num_splits, double scale,
+                            torch::Tensor tmp_out, torch::Tensor tmp_ml,
+                            torch::Tensor prefix_blocks, torch::Tensor tiles,
+                            int64_t prefix_splits);
+void paged_attention_rope_shared(
+    torch::Tensor out, torch::Tensor qkv, torch::Tensor k_cache,
+    torch::Tensor v_cache, torch::Tensor cos_sin, torch::Tensor positions,
+    torch::Tensor block_table, torch::Tensor seq_lens, int64_t num_q_heads,
+    int64_t num_kv_heads, int64_t num_splits, double scale,
+    torch::Tensor tmp_out, torch::Tensor tmp_ml, torch::Tensor prefix_blocks,
+    torch::Tensor tiles, int64_t prefix_splits);
 void prefill_attention(torch::Tensor out, torch::Tensor q,
                        torch::Tensor k_cache, torch::Tensor v_cache,
                        torch::Tensor block_table, torch::Tensor seq_lens,
@@ -102,6 +116,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "decode paged attention (GQA, split-KV)");
   m.def("paged_attention_rope", &kukeon::paged_attention_rope,
         "decode paged attention with RoPE + KV append folded in");
+  m.def("paged_attention_shared", &kukeon::paged_attention_shared,
+        "decode paged attention, shared prefix blocks read once per tile of "
+        "rows");
+  m.def("paged_attention_rope_shared", &kukeon::paged_attention_rope_shared,
+        "paged_attention_rope, shared prefix blocks read once per tile of "
+        "rows");
   m.def("prefill_attention", &kukeon::prefill_attention,
         "varlen causal paged prefill attention (MFMA)");
   m.def("mfma_probe", &kukeon::mfma_probe,

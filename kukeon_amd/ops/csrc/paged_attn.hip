@@ -96,7 +96,16 @@ DEV_INLINE float merge_weight(float m_s, float M) {
 
 constexpr int kWaveLds = 2 * 128 * 16 * 2;  // two V^T images: 8 KiB
 
-template <bool FP8, bool ROPE>
+// Trailing kernel argument of paged_attn_kernel: empty for the plain op, so
+// its four instantiations keep their code; the suffix pass of the
+// shared-prefix op gets the per-row prefix length and the prefix slot count.
+struct NoPrefix {};
+struct PrefixArgs {
+  const int* prefix_blocks;  // [B] leading blocks a prefix tile covers
+  int prefix_splits;         // workspace slots in front of the suffix's
+};
+
+template <bool FP8, bool ROPE, bool SHARED = false>
 // 128 VGPRs (4 waves/SIMD) for both cache types. fp8 used to be bounded at
 // 3 waves/SIMD for headroom but compiled to 127 registers and so ran at 4;
 // with the prologue added here the looser bound let it drift to 131, which
@@ -115,7 +124,7 @@ __global__ __launch_bounds__(512, 4) void paged_attn_kernel(
     const int* __restrict__ block_table,  // [B, max_blocks]
     const int* __restrict__ seq_lens,     // [B]
     long q_stride, int Hq, int Hk, int max_blocks, int S, int merge,
-    float scale) {
+    float scale, std::conditional_t<SHARED, PrefixArgs, NoPrefix> px) {
   constexpr int D = 128;
   constexpr int BS = 16;
   const int b = blockIdx.x;
@@ -129,13 +138,21 @@ __global__ __launch_bounds__(512, 4) void paged_attn_kernel(
   const int ctx = seq_lens[b];
 
   const int nblocks = ctx > 0 ? (ctx + BS - 1) / BS : 0;
-  const int per_slot = (nblocks + S - 1) / S;
+  // SHARED (suffix pass): blocks [0, pb) are the prefix kernel's; the S
+  // slots cut [pb, nblocks) and land behind the prefix slots
+  int pb = 0;
+  if constexpr (SHARED) pb = min(max(px.prefix_blocks[b], 0), nblocks);
+  const int per_slot = (nblocks - pb + S - 1) / S;
 
   const int pos = ROPE ? positions[b] : -1;
   if (ROPE && pos >= 0) {
     // ---- rotate K + append K/V: the one wave that will read the row ----
     const int pblk = pos / BS;
-    const int owner = pblk < nblocks ? pblk / per_slot : 0;
+    int owner;
+    if constexpr (SHARED)
+      owner = pblk >= pb && pblk < nblocks ? (pblk - pb) / per_slot : 0;
+    else
+      owner = pblk < nblocks ? pblk / per_slot : 0;
     if (slot == owner && pblk < max_blocks && lane < 16) {
       const unsigned short* krow =
           q + (long)b * q_stride + (long)(Hq + hk) * D;
@@ -185,7 +202,7 @@ __global__ __launch_bounds__(512, 4) void paged_attn_kernel(
   extern __shared__ __align__(16) unsigned short vtbuf_all[];
   unsigned short* const vtbuf0 = vtbuf_all + wid * (2 * D * BS);
 
-  const int blk_begin = slot * per_slot;
+  const int blk_begin = pb + slot * per_slot;
   const int blk_end = min(nblocks, blk_begin + per_slot);
   const int kv_hi = min(ctx, blk_end * BS);
 
@@ -352,7 +369,11 @@ __global__ __launch_bounds__(512, 4) void paged_attn_kernel(
     // ---- epilogue: unnormalized O + (m, l) into this wave's slot ----
     if (rc >= G) return;
     const int head = hk * G + rc;
-    float* top = tmp_out + (((long)b * Hq + head) * S + slot) * D;
+    long wslot = ((long)b * Hq + head) * S + slot;
+    if constexpr (SHARED)
+      wslot = ((long)b * Hq + head) * (px.prefix_splits + S) +
+              px.prefix_splits + slot;
+    float* top = tmp_out + wslot * D;
 #pragma unroll
     for (int dc = 0; dc < 8; ++dc) {
 #pragma unroll
@@ -361,7 +382,7 @@ __global__ __launch_bounds__(512, 4) void paged_attn_kernel(
       }
     }
     if (g4 == 0) {
-      float* ml = tmp_ml + (((long)b * Hq + head) * S + slot) * 2;
+      float* ml = tmp_ml + wslot * 2;
       ml[0] = m;
       ml[1] = l_acc;
     }
@@ -429,27 +450,273 @@ __global__ __launch_bounds__(512, 4) void paged_attn_kernel(
   }
 }
 
+// Shared-prefix pass of ops.paged_attention[_rope]_shared. Sessions forked
+// from one context hold the same leading cache blocks; with G < 16 the
+// kernel above leaves 16 - G MFMA columns as padding, and every session
+// fetches those blocks again. Here a tile of up to W = 16 / G sessions
+// rides the N axis together: column rc is (member rc / G, q head rc % G),
+// and the tile's prefix blocks are fetched, scored and softmaxed once.
+//
+// paged_attn_prefix_kernel<FP8, ROPE> — grid (T, Hk, ceil(PS / 4)), 4 waves.
+//   tiles[t] = {n_rows, n_prefix_blocks, member rows...} (kTileCols ints);
+//   n_rows == 0 is an empty tile, so the grid can stay fixed under graph
+//   replay while membership changes. The block ids come from the block
+//   table of the first member. Wave `slot` walks its own contiguous range
+//   of ceil(n_prefix_blocks / PS) blocks with the tile loop of the kernel
+//   above and writes unnormalised O and (m, l) of column rc into prefix
+//   slot `slot` of that member's row (O = 0, m = -inf, l = 0 for an empty
+//   range), all PS slots of every member on every call. The suffix pass
+//   (paged_attn_kernel<.., SHARED>) fills the slots behind them and the
+//   reduce kernel merges both. No wave waits on another, no barrier.
+//   - Q is read per column from that member's row and, with ROPE, rotated
+//     at that member's position, exactly as the kernel above does.
+//   - Every prefix block is full and below every member's context, so no
+//     score is masked. The V-row zeroing is dead for the same reason — it
+//     guards rows at or past kv_hi, and here kv_hi is the end of the range —
+//     and is left out.
+//   - Nothing is appended here: the new token's block is never a prefix
+//     block, so this kernel only reads the caches and may overlap the
+//     suffix pass.
+//   - n_rows, n_prefix_blocks and the member rows are clamped to what the
+//     buffers hold, so bad metadata computes nonsense but stays in bounds.
+constexpr int kTileCols = 2 + 16;
+
+template <bool FP8, bool ROPE>
+__global__ __launch_bounds__(256, 4) void paged_attn_prefix_kernel(
+    float* __restrict__ tmp_out,          // [B, Hq, Stot, D] f32
+    float* __restrict__ tmp_ml,           // [B, Hq, Stot, 2]
+    const unsigned short* __restrict__ q, // [B, q_stride]; ROPE: qkv rows
+    const void* __restrict__ k_cache,     // [NB, Hk, 16, D]
+    const void* __restrict__ v_cache,
+    const float* __restrict__ cos_sin,    // [max_pos, D]   (ROPE)
+    const int* __restrict__ positions,    // [B]            (ROPE)
+    const int* __restrict__ block_table,  // [B, max_blocks]
+    const int* __restrict__ tiles,        // [T, kTileCols]
+    long q_stride, int B, int Hq, int Hk, int max_blocks, int PS, int Stot,
+    float scale) {
+  constexpr int D = 128;
+  constexpr int BS = 16;
+  const int hk = blockIdx.y;
+  // wave-uniform, and told so: slot, the block range and the loop counter
+  // then live in scalar registers
+  const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE);
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int g4 = lane >> 4;       // 0..3
+  const int rc = lane & 15;
+  const int G = Hq / Hk;
+  const int slot = blockIdx.z * (blockDim.x / WAVE) + wid;
+  const int* tile = tiles + (long)blockIdx.x * kTileCols;
+  const int n_rows = min(tile[0], 16 / G);
+  if (n_rows <= 0 || slot >= PS) return;
+  const int npb = min(max(tile[1], 0), max_blocks);
+  const int row0 = min(max(tile[2], 0), B - 1);
+  // column -> (member, head); padding columns shadow member 0
+  const bool live = rc / G < n_rows;
+  const int row = live ? min(max(tile[2 + rc / G], 0), B - 1) : row0;
+  const int qh = rc % G;
+
+  extern __shared__ __align__(16) unsigned short vtbuf_all[];
+  unsigned short* const vtbuf0 = vtbuf_all + wid * (2 * D * BS);
+
+  const int per_slot = (npb + PS - 1) / PS;
+  const int blk_begin = slot * per_slot;
+  const int blk_end = min(npb, blk_begin + per_slot);
+
+  unsigned int qf[4][4];
+  {
+    const unsigned short* qp =
+        q + (long)row * q_stride + (long)(hk * G + qh) * D;
+    bf16x8 qv[4];
+#pragma unroll
+    for (int st = 0; st < 4; ++st)
+      qv[st] = load_bf16x8(qp + st * 32 + g4 * 8);
+    const int pos = ROPE ? positions[row] : -1;
+    if (ROPE && pos >= 0) {
+      const float* cs = cos_sin + (long)pos * D;
+#pragma unroll
+      for (int st = 0; st < 2; ++st) {
+        const int d0 = st * 32 + g4 * 8;
+        float xo[8], yo[8];
+        rope_rotate8(qv[st], qv[st + 2], cs + d0, cs + D / 2 + d0, xo, yo);
+        qv[st].raw = pack_bf16x8(xo);
+        qv[st + 2].raw = pack_bf16x8(yo);
+      }
+    }
+#pragma unroll
+    for (int st = 0; st < 4; ++st) {
+      const uint4 v = qv[st].raw;
+      qf[st][0] = v.x; qf[st][1] = v.y; qf[st][2] = v.z; qf[st][3] = v.w;
+    }
+  }
+
+  float m = -INFINITY, l_acc = 0.f;
+  f32x4_t oacc[8] = {{}, {}, {}, {}, {}, {}, {}, {}};
+
+  const auto* kc = reinterpret_cast<const kv_elem_t<FP8>*>(k_cache);
+  const auto* vc = reinterpret_cast<const kv_elem_t<FP8>*>(v_cache);
+  const int* bt0 = block_table + (long)row0 * max_blocks;
+
+  // K fragments, V staging and the V^T image as in paged_attn_kernel
+  uint4 kfr[4];
+  auto kfetch = [&](int bi_f) {
+    const long base = ((long)bt0[bi_f] * Hk + hk) * BS * D;
+    const long off = base + (long)rc * D + g4 * 8;
+#pragma unroll
+    for (int st = 0; st < 4; ++st)
+      kfr[st] = load_kv8(kc + off + st * 32);
+  };
+  const int stg_d0 = rc * 8;
+  uint4 vpre[2][2];
+  auto vfetch = [&](int bi_f) {
+    const long base = ((long)bt0[bi_f] * Hk + hk) * BS * D;
+#pragma unroll
+    for (int pass = 0; pass < 2; ++pass) {
+      const int kp = pass * 4 + g4;
+      vpre[pass][0] = load_kv8(vc + base + (long)(2 * kp) * D + stg_d0);
+      vpre[pass][1] = load_kv8(vc + base + (long)(2 * kp + 1) * D + stg_d0);
+    }
+  };
+  auto vwrite = [&](unsigned short* vt) {
+#pragma unroll
+    for (int pass = 0; pass < 2; ++pass) {
+      const int kp = pass * 4 + g4;
+      const uint4 r0 = vpre[pass][0];
+      const uint4 r1 = vpre[pass][1];
+      const unsigned int* a0 = reinterpret_cast<const unsigned int*>(&r0);
+      const unsigned int* a1 = reinterpret_cast<const unsigned int*>(&r1);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const unsigned short e0 = (a0[j >> 1] >> ((j & 1) * 16)) & 0xffffu;
+        const unsigned short e1 = (a1[j >> 1] >> ((j & 1) * 16)) & 0xffffu;
+        const unsigned int packed = (unsigned)e0 | ((unsigned)e1 << 16);
+        const int d = stg_d0 + j;
+        const int byte = d * 32 + ((4 * kp) ^ ((d & 3) << 3));
+        *reinterpret_cast<unsigned int*>(
+            reinterpret_cast<char*>(vt) + byte) = packed;
+      }
+    }
+  };
+
+  if (blk_begin < blk_end) {
+    kfetch(blk_begin);
+    vfetch(blk_begin);
+    vwrite(vtbuf0 + (blk_begin & 1) * (D * BS));
+  }
+
+  for (int bi = blk_begin; bi < blk_end; ++bi) {
+    const unsigned short* vt = vtbuf0 + (bi & 1) * (D * BS);
+
+    f32x4_t sacc = {};
+#pragma unroll
+    for (int st = 0; st < 4; ++st) {
+      sacc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+          as_frag(kfr[st].x, kfr[st].y, kfr[st].z, kfr[st].w),
+          as_frag(qf[st][0], qf[st][1], qf[st][2], qf[st][3]),
+          sacc, 0, 0, 0);
+    }
+    if (bi + 1 < blk_end) kfetch(bi + 1);
+
+    // ---- online softmax, one column = one (member, head) ----
+    float sv[4];
+    float tmax = -INFINITY;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      sv[r] = sacc[r] * scale;
+      tmax = fmaxf(tmax, sv[r]);
+    }
+    tmax = fmaxf(tmax, __shfl_xor(tmax, 16, WAVE));
+    tmax = fmaxf(tmax, __shfl_xor(tmax, 32, WAVE));
+    const float mn = fmaxf(m, tmax);
+    const float alpha = (m == -INFINITY) ? 0.f : __expf(m - mn);
+    m = mn;
+    float psum = 0.f;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      sv[r] = __expf(sv[r] - mn);
+      psum += sv[r];
+    }
+    psum += __shfl_xor(psum, 16, WAVE);
+    psum += __shfl_xor(psum, 32, WAVE);
+    l_acc = l_acc * alpha + psum;
+#pragma unroll
+    for (int dc = 0; dc < 8; ++dc)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) oacc[dc][r] *= alpha;
+
+    if (bi + 1 < blk_end) {
+      vfetch(bi + 1);
+      vwrite(vtbuf0 + ((bi + 1) & 1) * (D * BS));
+    }
+
+    const bf16x4_t pfrag = as_frag(cvtpk_bf16(sv[0], sv[1]),
+                                   cvtpk_bf16(sv[2], sv[3]));
+#pragma unroll
+    for (int dc = 0; dc < 8; ++dc) {
+      const int d = dc * 16 + rc;
+      const int byte = d * 32 + ((8 * g4) ^ ((d & 3) << 3));
+      const uint2 vf = *reinterpret_cast<const uint2*>(
+          reinterpret_cast<const char*>(vt) + byte);
+      oacc[dc] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(
+          as_frag(vf.x, vf.y), pfrag, oacc[dc], 0, 0, 0);
+    }
+  }
+
+  // The epilogue derives its lane indices and the member row afresh (lane
+  // id from mbcnt, the row through a volatile load the prologue's cannot be
+  // merged with), so nothing of it lives across the tile loop: the fp8
+  // variant spilled those registers otherwise.
+  const int oln = __lane_id();
+  const int om = (oln & 15) / G;
+  if (om >= n_rows) return;
+  const int og4 = oln >> 4;
+  const int orow =
+      min(max(const_cast<const volatile int*>(tile)[2 + om], 0), B - 1);
+  const long wslot =
+      ((long)orow * Hq + hk * G + (oln & 15) % G) * Stot + slot;
+  float* top = tmp_out + wslot * D;
+#pragma unroll
+  for (int dc = 0; dc < 8; ++dc) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      top[dc * 16 + 4 * og4 + r] = oacc[dc][r];
+    }
+  }
+  if (og4 == 0) {
+    float* ml = tmp_ml + wslot * 2;
+    ml[0] = m;
+    ml[1] = l_acc;
+  }
+}
+
 // Merge the S split partials of head (b, h); thread d owns output dim d.
 // All S slots are read unconditionally (see the slot rule above) — no
 // per-split block math, no zero-ctx division hazard.
-template <int D>
+//
+// SHARED (shared-prefix op): S counts the prefix slots and the suffix slots
+// behind them. The prefix kernel writes the prefix slots of tile members
+// only, so a row in no tile (prefix_blocks == 0) starts at the first suffix
+// slot: no slot is read that this call did not write. An empty slot weighs
+// 0 in every expression below, so skipping those changes no bit.
+template <int D, bool SHARED = false>
 __global__ void paged_attn_reduce_kernel(
     unsigned short* __restrict__ out, const float* __restrict__ tmp_out,
     const float* __restrict__ tmp_ml, const int* __restrict__ seq_lens,
-    int Hq, int S) {
+    int Hq, int S, std::conditional_t<SHARED, PrefixArgs, NoPrefix> px) {
   const int b = blockIdx.x;
   const int h = blockIdx.y;
   const int d = threadIdx.x;
   if (seq_lens[b] <= 0) return;
+  int s0 = 0;
+  if constexpr (SHARED) s0 = px.prefix_blocks[b] > 0 ? 0 : px.prefix_splits;
   const float* ml = tmp_ml + (((long)b * Hq + h) * S) * 2;
   float M = -INFINITY;
-  for (int s = 0; s < S; ++s) M = fmaxf(M, ml[s * 2]);
+  for (int s = s0; s < S; ++s) M = fmaxf(M, ml[s * 2]);
   float L = 0.f;
-  for (int s = 0; s < S; ++s)
+  for (int s = s0; s < S; ++s)
     L = __builtin_fmaf(merge_weight(ml[s * 2], M), ml[s * 2 + 1], L);
   const float* top = tmp_out + (((long)b * Hq + h) * S) * D;
   float acc = 0.f;
-  for (int s = 0; s < S; ++s) {
+  for (int s = s0; s < S; ++s) {
     const float w = merge_weight(ml[s * 2], M);
     acc = __builtin_fmaf(w, top[(long)s * D + d], acc);
   }
@@ -461,6 +728,19 @@ __global__ void paged_attn_reduce_kernel(
 // the fused qkv projection [B, (Hq+2*Hk)*128]: q and the new k are rotated
 // on the fly and the new k/v rows appended to the caches; qkv itself is
 // not written. All checks are on host-side metadata; nothing is allocated.
+//
+// With `shared` (the *_shared ops) the leading prefix_blocks[b] blocks of a
+// row are attended to by the prefix kernel, a tile of sibling rows at a
+// time, into workspace slots [0, prefix_splits); this kernel's suffix pass
+// walks the rest into the num_splits slots behind them and the reduce
+// kernel merges all of them, so the workspaces hold
+// B*Hq*(prefix_splits + num_splits) slots. What the caller guarantees about
+// the tiles is in ops.paged_attention_shared; none of it is read here.
+struct SharedPrefix {
+  torch::Tensor prefix_blocks, tiles;
+  int64_t prefix_splits;
+};
+
 static void decode_attention(torch::Tensor out, torch::Tensor q,
                              torch::Tensor k_cache, torch::Tensor v_cache,
                              const torch::Tensor* cos_sin,
@@ -468,7 +748,8 @@ static void decode_attention(torch::Tensor out, torch::Tensor q,
                              torch::Tensor block_table, torch::Tensor seq_lens,
                              int64_t q_offset, int64_t num_splits,
                              double scale, torch::Tensor tmp_out,
-                             torch::Tensor tmp_ml) {
+                             torch::Tensor tmp_ml,
+                             const SharedPrefix* shared = nullptr) {
   const int B = q.size(0);
   if (B == 0) return;
   TORCH_CHECK(k_cache.dim() == 4 && k_cache.size(2) == 16 &&
@@ -508,7 +789,21 @@ static void decode_attention(torch::Tensor out, torch::Tensor q,
                   seq_lens.is_contiguous() && seq_lens.numel() >= B,
               "seq_lens must be contiguous int32 [>= B]");
   TORCH_CHECK(num_splits >= 1, "num_splits must be >= 1");
-  const int64_t slots = (int64_t)B * Hq * num_splits;
+  const int64_t PS = shared ? shared->prefix_splits : 0;
+  if (shared) {
+    TORCH_CHECK(PS >= 1, "prefix_splits must be >= 1");
+    const auto& pb = shared->prefix_blocks;
+    const auto& tl = shared->tiles;
+    TORCH_CHECK(pb.scalar_type() == torch::kInt32 && pb.is_contiguous() &&
+                    pb.dim() == 1 && pb.numel() >= B,
+                "prefix_blocks must be contiguous int32 [>= B]");
+    TORCH_CHECK(tl.scalar_type() == torch::kInt32 && tl.is_contiguous() &&
+                    tl.dim() == 2 && tl.size(1) == kTileCols,
+                "tiles must be contiguous int32 [T, 2 + 16]");
+    TORCH_CHECK(pb.device() == q.device() && tl.device() == q.device(),
+                "all tensors must be on the same GPU");
+  }
+  const int64_t slots = (int64_t)B * Hq * (PS + num_splits);
   TORCH_CHECK(tmp_out.scalar_type() == torch::kFloat32 &&
                   tmp_out.is_contiguous() && tmp_out.numel() >= slots * D,
               "tmp_out must be contiguous float32 with >= B*Hq*num_splits*128 "
@@ -547,11 +842,49 @@ static void decode_attention(torch::Tensor out, torch::Tensor q,
   // 4 or 8 waves when they fit — that workgroup merges them itself — else
   // 4-wave workgroups into the workspaces plus the reduce kernel.
   const int S = (int)num_splits;
-  const bool merge = S <= 8;
-  const int waves = merge && S > 4 ? 8 : 4;
   auto stream = c10::hip::getCurrentHIPStream().stream();
   const unsigned short* qp =
       reinterpret_cast<const unsigned short*>(q.data_ptr()) + q_offset;
+  if (shared) {
+    // prefix kernel -> suffix pass -> reduce, all through the workspaces
+    const int T = shared->tiles.size(0);
+    const int Stot = (int)PS + S;
+    const PrefixArgs px{shared->prefix_blocks.data_ptr<int>(), (int)PS};
+    if (T > 0) {
+      auto* prefix = fp8 ? (rope ? paged_attn_prefix_kernel<true, true>
+                                 : paged_attn_prefix_kernel<true, false>)
+                         : (rope ? paged_attn_prefix_kernel<false, true>
+                                 : paged_attn_prefix_kernel<false, false>);
+      prefix<<<dim3(T, Hk, (unsigned)((PS + 3) / 4)), 4 * WAVE, 4 * kWaveLds,
+               stream>>>(
+          tmp_out.data_ptr<float>(), tmp_ml.data_ptr<float>(), qp,
+          k_cache.data_ptr(), v_cache.data_ptr(), csp, posp,
+          block_table.data_ptr<int>(), shared->tiles.data_ptr<int>(),
+          q.stride(0), B, Hq, Hk, (int)block_table.size(1), (int)PS, Stot,
+          (float)scale);
+      HIP_CHECK_KERNEL();
+    }
+    auto* suffix = fp8 ? (rope ? paged_attn_kernel<true, true, true>
+                               : paged_attn_kernel<true, false, true>)
+                       : (rope ? paged_attn_kernel<false, true, true>
+                               : paged_attn_kernel<false, false, true>);
+    suffix<<<dim3(B, Hk, (unsigned)((S + 3) / 4)), 4 * WAVE, 4 * kWaveLds,
+             stream>>>(
+        reinterpret_cast<unsigned short*>(out.data_ptr()),
+        tmp_out.data_ptr<float>(), tmp_ml.data_ptr<float>(), qp,
+        k_cache.data_ptr(), v_cache.data_ptr(), csp, posp,
+        block_table.data_ptr<int>(), seq_lens.data_ptr<int>(), q.stride(0), Hq,
+        Hk, (int)block_table.size(1), S, 0, (float)scale, px);
+    HIP_CHECK_KERNEL();
+    paged_attn_reduce_kernel<128, true><<<dim3(B, Hq), 128, 0, stream>>>(
+        reinterpret_cast<unsigned short*>(out.data_ptr()),
+        tmp_out.data_ptr<float>(), tmp_ml.data_ptr<float>(),
+        seq_lens.data_ptr<int>(), Hq, Stot, px);
+    HIP_CHECK_KERNEL();
+    return;
+  }
+  const bool merge = S <= 8;
+  const int waves = merge && S > 4 ? 8 : 4;
   auto* launch = fp8 ? (rope ? paged_attn_kernel<true, true>
                              : paged_attn_kernel<true, false>)
                      : (rope ? paged_attn_kernel<false, true>
@@ -562,13 +895,13 @@ static void decode_attention(torch::Tensor out, torch::Tensor q,
       tmp_out.data_ptr<float>(), tmp_ml.data_ptr<float>(), qp,
       k_cache.data_ptr(), v_cache.data_ptr(), csp, posp,
       block_table.data_ptr<int>(), seq_lens.data_ptr<int>(), q.stride(0), Hq,
-      Hk, (int)block_table.size(1), S, (int)merge, (float)scale);
+      Hk, (int)block_table.size(1), S, (int)merge, (float)scale, NoPrefix{});
   HIP_CHECK_KERNEL();
   if (merge) return;
   paged_attn_reduce_kernel<128><<<dim3(B, Hq), 128, 0, stream>>>(
       reinterpret_cast<unsigned short*>(out.data_ptr()),
       tmp_out.data_ptr<float>(), tmp_ml.data_ptr<float>(),
-      seq_lens.data_ptr<int>(), Hq, S);
+      seq_lens.data_ptr<int>(), Hq, S, NoPrefix{});
   HIP_CHECK_KERNEL();
 }
 
@@ -597,6 +930,38 @@ void paged_attention_rope(torch::Tensor out, torch::Tensor qkv,
   decode_attention(out, qkv, k_cache, v_cache, &cos_sin, &positions,
                    block_table, seq_lens, 0, num_splits, scale, tmp_out,
                    tmp_ml);
+}
+
+// paged_attention / paged_attention_rope with the leading blocks that
+// sibling rows share attended to once per tile of rows.
+void paged_attention_shared(torch::Tensor out, torch::Tensor q,
+                            torch::Tensor k_cache, torch::Tensor v_cache,
+                            torch::Tensor block_table, torch::Tensor seq_lens,
+                            int64_t q_offset, int64_t num_splits, double scale,
+                            torch::Tensor tmp_out, torch::Tensor tmp_ml,
+                            torch::Tensor prefix_blocks, torch::Tensor tiles,
+                            int64_t prefix_splits) {
+  const SharedPrefix sp{prefix_blocks, tiles, prefix_splits};
+  decode_attention(out, q, k_cache, v_cache, nullptr, nullptr, block_table,
+                   seq_lens, q_offset, num_splits, scale, tmp_out, tmp_ml,
+                   &sp);
+}
+
+void paged_attention_rope_shared(
+    torch::Tensor out, torch::Tensor qkv, torch::Tensor k_cache,
+    torch::Tensor v_cache, torch::Tensor cos_sin, torch::Tensor positions,
+    torch::Tensor block_table, torch::Tensor seq_lens, int64_t num_q_heads,
+    int64_t num_kv_heads, int64_t num_splits, double scale,
+    torch::Tensor tmp_out, torch::Tensor tmp_ml, torch::Tensor prefix_blocks,
+    torch::Tensor tiles, int64_t prefix_splits) {
+  TORCH_CHECK(out.dim() == 2 && out.size(1) == num_q_heads * 128 &&
+                  k_cache.dim() == 4 && k_cache.size(1) == num_kv_heads,
+              "out must be [B, num_q_heads*128] and the caches "
+              "[NB, num_kv_heads, 16, 128]");
+  const SharedPrefix sp{prefix_blocks, tiles, prefix_splits};
+  decode_attention(out, qkv, k_cache, v_cache, &cos_sin, &positions,
+                   block_table, seq_lens, 0, num_splits, scale, tmp_out,
+                   tmp_ml, &sp);
 }
 
 }  // namespace kukeon

@@ -156,6 +156,92 @@ def paged_attention_rope(out: torch.Tensor, qkv: torch.Tensor,
                     num_splits, scale, tmp_out, tmp_ml)
 
 
+TILE_COLS = 2 + 16   # n_rows, n_prefix_blocks, up to 16 member rows
+
+
+def check_prefix_tiles(tiles: torch.Tensor, group: int) -> None:
+    """The part of the shared-prefix contract that needs only the tiles
+    (on the host): shape, and n_rows <= 16 // group in every tile."""
+    if tiles.dim() != 2 or tiles.shape[1] != TILE_COLS or \
+            tiles.dtype != torch.int32:
+        raise ValueError("tiles must be int32 [T, 2 + 16]")
+    width = 16 // group
+    for t, row in enumerate(tiles.tolist()):
+        if not 0 <= row[0] <= width:
+            raise ValueError(f"tile {t} has {row[0]} rows, a tile holds at "
+                             f"most 16 // {group} = {width}")
+        if row[0] and row[1] < 0:
+            raise ValueError(f"tile {t} has a negative prefix length")
+
+
+def _check_shared_prefix(block_table, seq_lens, last_pos, prefix_blocks,
+                         tiles, group: int, nrows: int, block: int) -> None:
+    """Everything ops.paged_attention_shared leaves to its caller, checked:
+    raises ValueError at the first violation. `last_pos[b]` is the highest
+    position row b attends to."""
+    check_prefix_tiles(tiles, group)
+    want = [0] * nrows
+    seen = set()
+    for t, row in enumerate(tiles.tolist()):
+        n, npb, members = row[0], row[1], row[2:2 + row[0]]
+        if n == 0:
+            continue
+        first = members[0]
+        for r in members:
+            if not 0 <= r < nrows:
+                raise ValueError(f"tile {t}: row {r} out of range")
+            if r in seen:
+                raise ValueError(f"row {r} is in more than one tile")
+            seen.add(r)
+            if int(seq_lens[r]) <= 0:
+                raise ValueError(f"tile {t}: member row {r} is not live")
+            if npb * block > int(last_pos[r]):
+                raise ValueError(
+                    f"tile {t}: {npb} prefix blocks reach the newest token "
+                    f"of row {r} (position {int(last_pos[r])})")
+            if npb > block_table.shape[1] or not torch.equal(
+                    block_table[r, :npb], block_table[first, :npb]):
+                raise ValueError(f"tile {t}: the block table of row {r} "
+                                 "does not begin with the tile's prefix")
+            want[r] = npb
+    got = prefix_blocks[:nrows].tolist()
+    if got != want:
+        raise ValueError(f"prefix_blocks {got} disagrees with the tiles, "
+                         f"which give {want}")
+
+
+def paged_attention_shared(out, q, k_cache, v_cache, block_table, seq_lens,
+                           q_offset: int, num_splits: int, scale: float,
+                           tmp_out, tmp_ml, prefix_blocks, tiles,
+                           prefix_splits: int) -> None:
+    """paged_attention after a strict check of the shared-prefix metadata:
+    sharing only changes which kernel reads which block, so the reference
+    result is the unshared one, exactly."""
+    B = q.shape[0]
+    G = (out.shape[1] // k_cache.shape[3]) // k_cache.shape[1]
+    _check_shared_prefix(block_table, seq_lens, seq_lens[:B] - 1,
+                         prefix_blocks, tiles, G, B, k_cache.shape[2])
+    paged_attention(out, q, k_cache, v_cache, block_table, seq_lens, q_offset,
+                    num_splits, scale, tmp_out, tmp_ml)
+
+
+def paged_attention_rope_shared(out, qkv, k_cache, v_cache, cos_sin,
+                                positions, block_table, seq_lens,
+                                num_q_heads: int, num_kv_heads: int,
+                                num_splits: int, scale: float, tmp_out,
+                                tmp_ml, prefix_blocks, tiles,
+                                prefix_splits: int) -> None:
+    """paged_attention_rope after the same strict check; the token being
+    appended (at positions[b]) must lie past the prefix."""
+    B = qkv.shape[0]
+    _check_shared_prefix(block_table, seq_lens, positions[:B],
+                         prefix_blocks, tiles, num_q_heads // num_kv_heads,
+                         B, k_cache.shape[2])
+    paged_attention_rope(out, qkv, k_cache, v_cache, cos_sin, positions,
+                         block_table, seq_lens, num_q_heads, num_kv_heads,
+                         num_splits, scale, tmp_out, tmp_ml)
+
+
 def prefill_attention(out: torch.Tensor, q: torch.Tensor,
                       k_cache: torch.Tensor, v_cache: torch.Tensor,
                       block_table: torch.Tensor, seq_lens: torch.Tensor,

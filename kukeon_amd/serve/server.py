@@ -197,6 +197,10 @@ class ModelhubServer:
                 "weight_dtype": getattr(self.engine.model, "weight_dtype",
                                         "bf16"),
                 "weight_bytes": _resident_weight_bytes(self.engine.model),
+                "shared_prefix_min_tokens":
+                    self.engine.ecfg.shared_prefix_min_tokens,
+                "shared_prefix_steps": self.engine.shared_prefix_steps,
+                "shared_prefix_rows": self.engine.shared_prefix_rows,
                 "turn_latency_ms": {"p50": pct(0.50), "p95": pct(0.95),
                                     "p99": pct(0.99),
                                     "n": len(lat)},
@@ -479,6 +483,11 @@ def build_parser() -> argparse.ArgumentParser:
                     help="GEMM weight storage; fp8 = e4m3 weight-only "
                          "quantisation with per-output-channel scales "
                          "(default: KUKEON_WEIGHT_DTYPE, else bf16)")
+    ap.add_argument("--shared-prefix-min-tokens", type=int, default=None,
+                    help="decode attention reads the KV prefix that forked "
+                         "sessions share once per tile of sessions when it "
+                         "has at least this many tokens; 0 = never "
+                         "(default: EngineConfig's)")
     return ap
 
 
@@ -493,6 +502,8 @@ def main(argv: Optional[List[str]] = None) -> None:
         max_model_len=args.max_model_len, max_sessions=args.max_sessions,
         num_kv_blocks=args.kv_blocks or (512 if device == "cpu" else 0),
         use_graphs=not args.no_graphs and device != "cpu" and not cfg.is_moe)
+    if args.shared_prefix_min_tokens is not None:
+        ecfg.shared_prefix_min_tokens = max(0, args.shared_prefix_min_tokens)
     if cfg.is_moe:
         from kukeon_amd.models.mixtral import MixtralModel
         model = MixtralModel(cfg, device=device,

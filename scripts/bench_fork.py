@@ -10,7 +10,11 @@ process, alternating, after one untimed round of each.
 
 Per round: seconds until every session has its first token, seconds for
 the whole round (both from a host clock around work that ends in a device
-synchronise), and the KV blocks in use when the last prefill finished.
+synchronise), their difference (the decode part), and the KV blocks in use
+when the last prefill finished. --shared-prefix-min-tokens N adds mode
+"fork_shared": fork with decode attention reading the shared prefix once
+per tile of sessions (EngineConfig.shared_prefix_min_tokens = N), in the
+same process and alternating with the others.
 Prints one JSON line.
 
     python scripts/bench_fork.py                  # 8B, 3072 + 256 + 128
@@ -45,7 +49,8 @@ def spread(xs):
             "min": round(min(xs), 4), "max": round(max(xs), 4), "n": len(xs)}
 
 
-def run_round(engine, mode, prefix, suffixes, decode_len, sync):
+def run_round(engine, mode, prefix, suffixes, decode_len, sync,
+              shared_min_tokens=0):
     alloc = engine.kv.allocator
     bs = engine.ecfg.block_size
     sp = SamplingParams(temperature=0.7, top_k=50, top_p=0.9,
@@ -53,7 +58,11 @@ def run_round(engine, mode, prefix, suffixes, decode_len, sync):
     n = len(suffixes)
     sync()
     t0 = time.perf_counter()
-    if mode == "fork":
+    # "fork_shared" is "fork" with the shared-prefix decode path on
+    engine.ecfg.shared_prefix_min_tokens = (
+        shared_min_tokens if mode == "fork_shared" else 0)
+    steps0 = engine.shared_prefix_steps
+    if mode in ("fork", "fork_shared"):
         template = SequenceKV(bs)
         engine.add_request(template, prefix,
                            SamplingParams(max_new_tokens=0))
@@ -83,6 +92,8 @@ def run_round(engine, mode, prefix, suffixes, decode_len, sync):
         engine.free_sequence(kv)
     assert alloc.num_free == alloc.num_blocks and alloc.num_shared == 0
     return {"first_token_s": t_first, "round_s": total,
+            "decode_s": total - t_first,
+            "shared_prefix_steps": engine.shared_prefix_steps - steps0,
             "blocks_used_after_prefill": used, "blocks_shared": shared}
 
 
@@ -136,6 +147,10 @@ def main():
     ap.add_argument("--kv-blocks", type=int, default=20000)
     ap.add_argument("--kv-dtype", choices=["bf16", "fp8"], default="bf16")
     ap.add_argument("--no-graphs", action="store_true")
+    ap.add_argument("--shared-prefix-min-tokens", type=int, default=0,
+                    help="also run mode fork_shared: fork with "
+                         "EngineConfig.shared_prefix_min_tokens set to this, "
+                         "alternating with the other modes")
     args = ap.parse_args()
     on_gpu = args.device != "cpu"
     if on_gpu and not torch.cuda.is_available():
@@ -164,13 +179,17 @@ def main():
                  for _ in range(args.suffix_len)]
                 for _ in range(args.sessions)]
     modes = ("fork", "prefill")
-    for m in modes:                      # warm every shape both modes use
-        run_round(engine, m, prefix, suffixes, args.decode_len, sync)
+    if args.shared_prefix_min_tokens > 0:
+        modes = ("fork", "fork_shared", "prefill")
+    for m in modes:                      # warm every shape the modes use
+        run_round(engine, m, prefix, suffixes, args.decode_len, sync,
+                  args.shared_prefix_min_tokens)
     rounds = {m: [] for m in modes}
     for _ in range(args.rounds):
         for m in modes:
             rounds[m].append(run_round(engine, m, prefix, suffixes,
-                                       args.decode_len, sync))
+                                       args.decode_len, sync,
+                                       args.shared_prefix_min_tokens))
     out = {"device": (torch.cuda.get_device_name(0) if on_gpu else "cpu"),
            "model": args.model, "sessions": args.sessions,
            "prefix_len": args.prefix_len, "suffix_len": args.suffix_len,
@@ -181,6 +200,9 @@ def main():
         out[m] = {
             "first_token_s": spread([r["first_token_s"] for r in rs]),
             "round_s": spread([r["round_s"] for r in rs]),
+            "decode_s": spread([r["decode_s"] for r in rs]),
+            "shared_prefix_steps":
+                sorted({r["shared_prefix_steps"] for r in rs}),
             "blocks_used_after_prefill":
                 sorted({r["blocks_used_after_prefill"] for r in rs}),
             "blocks_shared": sorted({r["blocks_shared"] for r in rs}),
