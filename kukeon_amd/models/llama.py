@@ -85,7 +85,7 @@ def _init_weight(shape, device, std=0.02, seed=None):
     return nn.Parameter(w, requires_grad=False)
 
 
-WEIGHT_DTYPES = ("bf16", "fp8")
+WEIGHT_DTYPES = ("bf16", "fp8", "mxfp4")
 
 
 def resolve_weight_dtype(weight_dtype: Optional[str]) -> str:
@@ -101,13 +101,13 @@ def resolve_weight_dtype(weight_dtype: Optional[str]) -> str:
 
 
 def _make_weight(shape, device, weight_dtype: str):
-    """A GEMM weight: the bf16 Parameter, or with fp8 its quantisation.
-    The bf16 tensor is drawn first and dropped right after, so the RNG
-    stream is the bf16 model's and peak memory is the fp8 model plus one
-    bf16 weight."""
+    """A GEMM weight: the bf16 Parameter, or with fp8 / mxfp4 its
+    quantisation. The bf16 tensor is drawn first and dropped right after,
+    so the RNG stream is the bf16 model's and peak memory is the
+    quantised model plus one bf16 weight."""
     w = _init_weight(shape, device)
-    if weight_dtype == "fp8":
-        return ops.quantize_weight(w.data)
+    if weight_dtype != "bf16":
+        return ops.quantize_weight(w.data, fmt=weight_dtype)
     return w
 
 
@@ -288,8 +288,10 @@ class LlamaModel(nn.Module):
     synthetic data / random weights — no checkpoints in this environment).
 
     weight_dtype "fp8" stores qkv/o/gate_up/down/lm_head as ops.Fp8Weight
-    (e4m3 bytes + per-output-channel scales, quantised per TP shard); the
-    embedding, the norms and the RoPE table stay as they are. None reads
+    (e4m3 bytes + per-output-channel scales, quantised per TP shard) and
+    "mxfp4" as ops.Mxfp4Weight (e2m1 codes + one e8m0 scale per 32 along
+    K, 0.53 bytes per element); the embedding, the norms and the RoPE
+    table stay as they are. None reads
     KUKEON_WEIGHT_DTYPE (default bf16)."""
 
     def __init__(self, cfg: ModelConfig, device="cuda",
@@ -324,7 +326,7 @@ class LlamaModel(nn.Module):
         """Bytes of device memory the model's weights hold."""
         n = sum(p.numel() * p.element_size() for p in self.parameters())
         return n + sum(w.nbytes for _, w in self.gemm_weights()
-                       if isinstance(w, ops.Fp8Weight))
+                       if isinstance(w, (ops.Fp8Weight, ops.Mxfp4Weight)))
 
     def _build_rope_table(self) -> torch.Tensor:
         cfg = self.cfg

@@ -294,8 +294,9 @@ class MixtralModel(nn.Module):
             # the expert weights run through bmm and the grouped GEMM,
             # which read bf16 only; quantising them is separate work
             raise ValueError(
-                "MixtralModel supports weight_dtype='bf16' only: fp8 "
-                "expert weights (bmm / grouped GEMM) are not implemented")
+                "MixtralModel supports weight_dtype='bf16' only: "
+                f"{self.weight_dtype} expert weights (bmm / grouped GEMM) "
+                "are not implemented")
         self.cfg = cfg
         self.device_ = torch.device(device)
         torch.manual_seed(43)

@@ -313,9 +313,46 @@ class Fp8Weight:
         return self.q.numel() + 4 * self.scale.numel()
 
 
+class Mxfp4Weight:
+    """A weight-only-quantised [N, K] weight in OCP MXFP4: `q` uint8
+    [N, K/2] holding two e2m1 codes per byte (element 2j in the low
+    nibble, 2j+1 in the high one; a code is sign, two exponent bits, one
+    mantissa bit: magnitudes 0, 0.5, 1, 1.5, 2, 3, 4, 6) and `scale` uint8
+    [N, K/32], one e8m0 byte per block of 32 along K; the weight it stands
+    for is value(code[n, k]) * 2^(scale[n, k // 32] - 127). Holding one
+    needs K % 32 == 0; the decode kernel N % 64 == 0 and K % 128 == 0."""
+
+    __slots__ = ("q", "scale")
+
+    def __init__(self, q: torch.Tensor, scale: torch.Tensor):
+        assert q.dtype == torch.uint8 and q.dim() == 2
+        assert q.shape[1] % 16 == 0
+        assert scale.dtype == torch.uint8 and scale.shape == (
+            q.shape[0], q.shape[1] // 16)
+        self.q = q
+        self.scale = scale
+
+    @property
+    def shape(self):
+        return (self.q.shape[0], 2 * self.q.shape[1])
+
+    @property
+    def device(self) -> torch.device:
+        return self.q.device
+
+    @property
+    def is_cuda(self) -> bool:
+        return self.q.is_cuda
+
+    @property
+    def nbytes(self) -> int:
+        return self.q.numel() + self.scale.numel()
+
+
 # bf16 scratch a wide-M (prefill, > 64 rows) linear dequantises an
-# Fp8Weight into, one per device, as large as the largest weight
-# quantised there; outgrown ones are pinned like the split-K workspaces
+# Fp8Weight or Mxfp4Weight into, one per device, as large as the largest
+# weight quantised there; outgrown ones are pinned like the split-K
+# workspaces
 _W8_SCRATCH = {}
 _W8_SCRATCH_RETIRED = []
 
@@ -333,24 +370,42 @@ def _w8_scratch(device: torch.device, numel: int) -> torch.Tensor:
     return buf
 
 
-def quantize_weight(w: torch.Tensor) -> Fp8Weight:
-    """Quantise a bf16 [N, K] weight to fp8 with per-output-channel
-    scales (scale = amax / 448, round-to-nearest-even)."""
+def quantize_weight(w: torch.Tensor, fmt: str = "fp8"):
+    """Quantise a bf16 [N, K] weight: fmt "fp8" to an Fp8Weight with
+    per-output-channel scales (scale = amax / 448, round-to-nearest-even),
+    fmt "mxfp4" to an Mxfp4Weight by the OCP MX rule
+    (reference.quantize_mxfp4_rows; K % 32 == 0)."""
     w = w.detach().contiguous()
     N, K = w.shape
-    q = torch.empty(N, K, dtype=torch.uint8, device=w.device)
-    scale = torch.empty(N, dtype=torch.float32, device=w.device)
-    _impl(w).quantize_fp8_rows(q, scale, w)
+    if fmt == "mxfp4":
+        if K % 32:
+            raise ValueError(f"mxfp4 needs K % 32 == 0, got K = {K}")
+        q = torch.empty(N, K // 2, dtype=torch.uint8, device=w.device)
+        scale = torch.empty(N, K // 32, dtype=torch.uint8, device=w.device)
+        _impl(w).quantize_mxfp4_rows(q, scale, w)
+        qw = Mxfp4Weight(q, scale)
+    elif fmt == "fp8":
+        q = torch.empty(N, K, dtype=torch.uint8, device=w.device)
+        scale = torch.empty(N, dtype=torch.float32, device=w.device)
+        _impl(w).quantize_fp8_rows(q, scale, w)
+        qw = Fp8Weight(q, scale)
+    else:
+        raise ValueError(f"quantize_weight: fmt must be 'fp8' or 'mxfp4', "
+                         f"got {fmt!r}")
     if w.is_cuda:
         _w8_scratch(w.device, N * K)
-    return Fp8Weight(q, scale)
+    return qw
 
 
-def dequantize_weight(fw: Fp8Weight, out: torch.Tensor = None) -> torch.Tensor:
-    """bf16(float(q) * scale) as [N, K]; into `out` when given."""
+def dequantize_weight(fw, out: torch.Tensor = None) -> torch.Tensor:
+    """The bf16 [N, K] weight an Fp8Weight (bf16(float(q) * scale)) or an
+    Mxfp4Weight (exact) stands for; into `out` when given."""
     if out is None:
         out = torch.empty(fw.shape, dtype=torch.bfloat16, device=fw.device)
-    _impl(fw.q).dequant_fp8_rows(out, fw.q, fw.scale)
+    if isinstance(fw, Mxfp4Weight):
+        _impl(fw.q).dequant_mxfp4_rows(out, fw.q, fw.scale)
+    else:
+        _impl(fw.q).dequant_fp8_rows(out, fw.q, fw.scale)
     return out
 
 
@@ -378,13 +433,39 @@ def _linear_w8(x: torch.Tensor, fw: Fp8Weight) -> torch.Tensor:
     return torch.nn.functional.linear(x, w)
 
 
+def _w4_skinny(x: torch.Tensor, mw: Mxfp4Weight) -> bool:
+    """Whether the W4A16 decode kernel runs x @ mw: its shape contract."""
+    N, K = mw.shape
+    return (x.is_cuda and x.dim() == 2 and 1 <= x.shape[0] <= 64
+            and x.dtype == torch.bfloat16 and x.is_contiguous()
+            and N % 64 == 0 and K % 128 == 0)
+
+
+def _linear_w4(x: torch.Tensor, mw: Mxfp4Weight) -> torch.Tensor:
+    if not x.is_cuda:
+        return reference.linear_w4(x, mw.q, mw.scale)
+    N, K = mw.shape
+    if _w4_skinny(x, mw):
+        out = torch.empty(x.shape[0], N, dtype=x.dtype, device=x.device)
+        ws = _skinny_workspace(x.device, "w4", N, K)
+        _native().skinny_gemm_w4(out, x, mw.q, mw.scale, ws)
+        return out
+    # prefill, the 96-256 row decode buckets, odd shapes: widen to bf16
+    # scratch (exact), then the library GEMM
+    w = _w8_scratch(x.device, N * K)[:N * K].view(N, K)
+    _native().dequant_mxfp4_rows(w, mw.q, mw.scale)
+    return torch.nn.functional.linear(x, w)
+
+
 def linear(x: torch.Tensor, w) -> torch.Tensor:
     """F.linear with the weight-streaming skinny-GEMM kernel on the decode
     shapes where it measured faster than hipBLASLt; hipBLASLt otherwise.
-    An Fp8Weight runs the W8A16 kernel at up to 64 rows and dequantises
-    into scratch for the library above that."""
+    An Fp8Weight / Mxfp4Weight runs the W8A16 / W4A16 kernel at up to 64
+    rows and dequantises into scratch for the library above that."""
     if isinstance(w, Fp8Weight):
         return _linear_w8(x, w)
+    if isinstance(w, Mxfp4Weight):
+        return _linear_w4(x, w)
     kind = _skinny_kind(x, w, fused=False)
     if kind is None:
         return torch.nn.functional.linear(x, w)
@@ -420,6 +501,18 @@ def linear_add_rmsnorm(x: torch.Tensor, w: torch.Tensor,
                                                 residual, norm_weight, eps)
             return normed
         kind = None
+    elif isinstance(w, Mxfp4Weight):
+        from kukeon_amd import parallel
+        N, K = w.shape
+        if (_w4_skinny(x, w) and parallel.tp_size() == 1
+                and N % 2048 == 0 and N <= 8192):
+            normed = torch.empty(x.shape[0], N, dtype=x.dtype,
+                                 device=x.device)
+            ws = _skinny_workspace(x.device, "w4", N, K)
+            _native().skinny_gemm_w4_fused_norm(normed, x, w.q, w.scale, ws,
+                                                residual, norm_weight, eps)
+            return normed
+        kind = None
     else:
         kind = _skinny_kind(x, w, fused=True)
     if kind is None:
@@ -452,8 +545,10 @@ def mlp_down_fused(gu: torch.Tensor, w: torch.Tensor,
     """
     rows = gu.shape[0]
     N, K = w.shape
-    # the silu-into-staging kernel reads bf16 W: an Fp8Weight goes unfused
-    if (_FUSE_SILU and not isinstance(w, Fp8Weight) and gu.dim() == 2
+    # the silu-into-staging kernel reads bf16 W: a quantised weight goes
+    # unfused
+    if (_FUSE_SILU and not isinstance(w, (Fp8Weight, Mxfp4Weight))
+            and gu.dim() == 2
             and gu.shape[1] == 2 * K
             and _skinny_kind(gu, w, fused=True) == "v5"):
         ws = _skinny_workspace(gu.device, "v5_fused", N, K)

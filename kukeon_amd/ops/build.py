@@ -31,6 +31,7 @@ SOURCES = [
     "moe_grouped.hip",
     "skinny_gemm.hip",
     "fp8_weight.hip",
+    "mxfp4_weight.hip",
     "bindings.cpp",
 ]
 

@@ -82,6 +82,16 @@ void skinny_gemm_w8_fused_norm(torch::Tensor normed, torch::Tensor x,
 void quantize_fp8_rows(torch::Tensor q, torch::Tensor scale, torch::Tensor w);
 void dequant_fp8_rows(torch::Tensor out, torch::Tensor q,
                       torch::Tensor scale);
+void skinny_gemm_w4(torch::Tensor out, torch::Tensor x, torch::Tensor q,
+                    torch::Tensor scale, torch::Tensor ws);
+void skinny_gemm_w4_fused_norm(torch::Tensor normed, torch::Tensor x,
+                               torch::Tensor q, torch::Tensor scale,
+                               torch::Tensor ws, torch::Tensor residual,
+                               torch::Tensor nw, double eps);
+void quantize_mxfp4_rows(torch::Tensor q, torch::Tensor scale,
+                         torch::Tensor w);
+void dequant_mxfp4_rows(torch::Tensor out, torch::Tensor q,
+                        torch::Tensor scale);
 void sample(torch::Tensor tokens, torch::Tensor logits, torch::Tensor temps,
             torch::Tensor top_k, torch::Tensor top_p, torch::Tensor seed,
             torch::Tensor workspace);
@@ -143,7 +153,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "weight-streaming decode GEMM (M<=64)");
   m.def("skinny_splitk", &kukeon::skinny_splitk,
         "split-K factor the skinny launcher of `kind` (v1, v2, v5, v5_fused, "
-        "v6, w8) uses for [N, K]; host-only",
+        "v6, w8, w4) uses for [N, K]; host-only",
         py::arg("kind"), py::arg("N"), py::arg("K"));
   m.def("glds_probe", &kukeon::glds_probe,
         "asm global_lds round-trip validator");
@@ -159,6 +169,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "bf16 [N,K] -> e4m3fn bytes + per-row f32 scale (amax/448)");
   m.def("dequant_fp8_rows", &kukeon::dequant_fp8_rows,
         "out = bf16(fp8(q) * scale[n])");
+  m.def("skinny_gemm_w4", &kukeon::skinny_gemm_w4,
+        "W4A16 decode GEMM: x @ mxfp4(q, scale)^T, M<=64");
+  m.def("skinny_gemm_w4_fused_norm", &kukeon::skinny_gemm_w4_fused_norm,
+        "W4A16 decode GEMM + split-K reduce + residual add + RMSNorm");
+  m.def("quantize_mxfp4_rows", &kukeon::quantize_mxfp4_rows,
+        "bf16 [N,K] -> e2m1 pairs [N,K/2] + e8m0 scale [N,K/32] (OCP MX)");
+  m.def("dequant_mxfp4_rows", &kukeon::dequant_mxfp4_rows,
+        "out = bf16(e2m1(q) * 2^(scale[n, k/32] - 127))");
   m.def("sample", &kukeon::sample, "top-k/top-p/temperature sampling");
   m.def("decode_advance", &kukeon::decode_advance,
         "on-device decode cursor advance (self-advancing graph)");

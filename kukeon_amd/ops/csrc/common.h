@@ -105,6 +105,33 @@ DEV_INLINE uint2 pack_fp8x8(const float* f) {
   return uint2{w0, w1};
 }
 
+// ---------- MXFP4 (OCP e2m1 codes + e8m0 block scale) helpers ----------
+typedef __attribute__((__vector_size__(2 * sizeof(__bf16)))) __bf16 bf16x2_cvt_t;
+
+// e8m0 scale byte in [1, 254] -> 2^(byte - 127) as f32: the byte is the
+// exponent field
+DEV_INLINE float e8m0_to_f32(unsigned int byte) {
+  return __builtin_bit_cast(float, byte << 23);
+}
+
+// 8 e2m1 codes (one dword, element j in nibble j) times `scale` -> 8 bf16:
+// one v_cvt_scalef32_pk_bf16_fp4 per byte, low nibble to the low half.
+// Exact while the results are normal bf16 numbers.
+DEV_INLINE uint4 fp4x8_to_bf16x8(unsigned int c, float scale) {
+  const bf16x2_cvt_t a0 =
+      __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(c, scale, 0);
+  const bf16x2_cvt_t a1 =
+      __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(c, scale, 1);
+  const bf16x2_cvt_t a2 =
+      __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(c, scale, 2);
+  const bf16x2_cvt_t a3 =
+      __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(c, scale, 3);
+  return uint4{__builtin_bit_cast(unsigned int, a0),
+               __builtin_bit_cast(unsigned int, a1),
+               __builtin_bit_cast(unsigned int, a2),
+               __builtin_bit_cast(unsigned int, a3)};
+}
+
 // ---------- wave reductions (wave64) ----------
 DEV_INLINE float wave_sum(float v) {
 #pragma unroll

@@ -20,10 +20,10 @@
 //
 // Layout of this file: the kernels first — v1 (above; o-projection), the
 // two split-K epilogues, v2 (G-tile walk, hand-counted waits), v5
-// (full-line W stream; down-projection), v6 (barrier-free) and W8A16
-// (fp8 weight bytes, per-row scales); v2, v6 and v5's silu path are
-// tested negative results. The host side sits at
-// the end: one split-K plan (skinny_plan, exported to Python as
+// (full-line W stream; down-projection), v6 (barrier-free), W8A16
+// (fp8 weight bytes, per-row scales) and W4A16 (MXFP4 codes, per-block
+// scales); v2, v6 and v5's silu path are tested negative results. The
+// host side sits at the end: one split-K plan (skinny_plan, exported to Python as
 // skinny_splitk so the workspace is sized by the same formula), one
 // launcher skeleton (run_reduce / run_reduce_add_rmsnorm), and one short
 // entry point per variant.
@@ -1152,6 +1152,216 @@ __global__ __launch_bounds__(256) void skinny_w8_kernel(
 }
 
 // ===========================================================================
+// W4A16: out[M,N] = x[M,K] @ deq(q, scale)^T with MXFP4 weights
+// (ops.Mxfp4Weight): q[N,K/2] two e2m1 codes per byte, scale[N,K/32] one
+// e8m0 byte per block of 32 along K.
+//
+// The W8 kernel's walk with a half-byte W stream. A lane's 16-B load is 32
+// k values of one row, which is exactly one MX block: one scale byte per
+// load. Four lane groups cover 128 k, so a 256-k slice is one whole 128-B
+// line per row, two loads per lane. Each dword of a load is 8 consecutive
+// k: v_cvt_scalef32_pk_bf16_fp4 widens it to a bf16x8 A fragment with the
+// block scale already applied (exact: a 2-bit significand times a power of
+// two), and the load's four fragments feed four MFMAs against x fragments
+// 8 k apart in the xswz image. The accumulator is therefore stored as it
+// is and both split-K epilogues are shared unchanged.
+//
+// Scale bytes: a slice has 8 per row and a lane needs the two at
+// kgrp and 4 + kgrp. Each lane fetches all 8 itself in one 8-byte load
+// (the four lane groups of a row read the same address), issued with the
+// slice's W loads into the same register set, and picks its bytes out
+// when it widens. That keeps every load a plain counted one (no LDS
+// staging or cross-lane traffic for 2 bytes), and the 16 rows' bytes sit
+// in lines that stay in L2 for the whole walk (a row of K = 4096 has 128
+// scale bytes, one line). A scale row is K/32 bytes, so with K%128 == 0
+// the load is dword-aligned, which is all a global dwordx2 load needs
+// (8-byte-aligned only when K%256 == 0); the type below says so. Two
+// dword loads instead are merged by hipcc into this same instruction,
+// and the explicit wait below has to know how many loads a slice is.
+// Not 1-byte loads: hipcc puts their zero-extend right behind the load,
+// which made it wait for the slice just issued in the middle of the
+// steady loop. Requires N%64 == 0 and K%128 == 0.
+// ===========================================================================
+constexpr int W4_U = KSLICE / 128;  // 16-B W loads per lane per full slice
+static_assert(W4_U == 2, "a slice's scale bytes are one 8-byte load");
+constexpr int W4_LOADS = W4_U + 1;  // VM ops per lane per full slice
+
+struct __attribute__((packed, aligned(4))) W4Scales {
+  unsigned int s[W4_U];  // e8m0 bytes of 128 k each, one per lane group
+};
+
+struct W4Regs {
+  u32x4_t w[W4_U];
+  unsigned int s[W4_U];
+};
+
+template <int MT>
+DEV_INLINE void w4_consume(u32x4_t wv, unsigned int sdword, int kgrp,
+                           const unsigned short* xb, f32x4_t (&acc)[MT],
+                           int kc0, int row16) {
+  const float s = e8m0_to_f32((sdword >> (8 * kgrp)) & 0xffu);
+#pragma unroll
+  for (int d = 0; d < 4; ++d) {
+    const bf16x8_t afrag = frag_of(fp4x8_to_bf16x8(wv[d], s));
+    const int kc = kc0 + 8 * d;
+#pragma unroll
+    for (int m = 0; m < MT; ++m) {
+      const int xr = m * 16 + row16;
+      const uint4 xv = *reinterpret_cast<const uint4*>(
+          reinterpret_cast<const char*>(xb) + xswz(xr, kc * 2));
+      acc[m] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+          afrag, frag_of(xv), acc[m], 0, 0, 0);
+    }
+  }
+}
+
+template <int MT, bool SPLIT>
+__global__ __launch_bounds__(256) void skinny_w4_kernel(
+    unsigned short* __restrict__ out,         // [M, N] bf16 (SPLIT=false)
+    float* __restrict__ ws,                   // [splitk, M, N] f32 (SPLIT)
+    const unsigned short* __restrict__ x,     // [M, K] bf16
+    const unsigned char* __restrict__ q,      // [N, K/2] e2m1 pairs
+    const unsigned char* __restrict__ scale,  // [N, K/32] e8m0
+    int M, int N, long K) {
+  __shared__ __align__(16) unsigned short xbuf[2][64 * KSLICE];
+  const int wid = threadIdx.x / WAVE;
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int n0 = blockIdx.x * 64 + wid * 16;     // this wave's 16 N rows
+  const int row16 = lane & 15;                   // A row / B col
+  const int kgrp = lane >> 4;                    // 0..3 -> k = 32*kgrp + j
+  f32x4_t acc[MT];
+#pragma unroll
+  for (int m = 0; m < MT; ++m) acc[m] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+
+  // the W8 kernel's walk: `nfull` whole slices ks0 + i*kstride, then the
+  // short tail slice (K % 256 == 128) if it falls to this block
+  const long kstride = (long)gridDim.y * KSLICE;
+  const long ks0 = (long)blockIdx.y * KSLICE;
+  if (ks0 >= K) return;  // never: the plan clamps splitk to the slices
+  const int nall = (int)((K - ks0 + kstride - 1) / kstride);
+  const bool has_tail = ks0 + (long)(nall - 1) * kstride + KSLICE > K;
+  const int nfull = nall - (has_tail ? 1 : 0);
+  const unsigned char* wrow =
+      q + (long)(n0 + row16) * (K / 2) + ks0 / 2 + 16 * kgrp;
+  const unsigned char* srow =
+      scale + (long)(n0 + row16) * (K / 32) + ks0 / 32;
+
+  // Three register sets rotate as in the W8 kernel: two slices of W (and
+  // their scale bytes) stay in flight while a third is consumed. A set is
+  // W4_LOADS plain loads, so at the top of slice i the VM queue holds
+  // W(i), DMA(i), W(i+1), oldest first, and the explicit wait leaves
+  // exactly W(i+1)'s W4_LOADS loads in flight: every DMA is older than
+  // all the plain loads the wait counts (profiles/r02_progress.md item 1).
+  W4Regs wa[3];
+  auto issue = [&](W4Regs& r, int i) {
+#pragma unroll
+    for (int u = 0; u < W4_U; ++u)
+      r.w[u] = nt_load16(wrow + (long)i * (kstride / 2) + u * 64);
+    const W4Scales sc = *reinterpret_cast<const W4Scales*>(
+        srow + (long)i * (kstride / 32));
+#pragma unroll
+    for (int u = 0; u < W4_U; ++u) r.s[u] = sc.s[u];
+  };
+  auto stage = [&](int i) {
+    const long ks = ks0 + (long)i * kstride;
+    glds_stage_x(xbuf[i & 1], x, K, ks, (int)min((long)KSLICE, K - ks), M,
+                 wid, lane);
+  };
+  // AHEAD / ISSUE are compile-time for the W8 kernel's reason: no branch
+  // around a load in the steady loop, so hipcc's counted waits stay exact
+  auto slice = [&](auto ahead, auto do_issue, W4Regs& cur, W4Regs& nxt2,
+                   int i) {
+    asm volatile("s_waitcnt vmcnt(%c0)" ::"i"(decltype(ahead)::value
+                                                  ? W4_LOADS
+                                                  : 0)
+                 : "memory");
+    __syncthreads();
+    // make hipcc place its own wait for this slice's loads here, where
+    // its count is exact, not after the issues below (it cannot count
+    // the DMAs)
+#pragma unroll
+    for (int u = 0; u < W4_U; ++u)
+      asm volatile("" : "+v"(cur.w[u]), "+v"(cur.s[u]));
+    // safe without a second barrier: every wave finished reading the
+    // other x buffer (slice i-1) before it crossed this slice's barrier
+    if (i + 1 < nall) stage(i + 1);
+    if constexpr (decltype(do_issue)::value) issue(nxt2, i + 2);
+#pragma unroll
+    for (int u = 0; u < W4_U; ++u)
+      w4_consume<MT>(cur.w[u], cur.s[u], kgrp, xbuf[i & 1], acc,
+                     u * 128 + 32 * kgrp, row16);
+  };
+  constexpr std::true_type yes{};
+  constexpr std::false_type no{};
+  // the last two whole slices: nothing left to issue
+  auto last2 = [&](W4Regs& a, W4Regs& b, int i) {
+    slice(yes, no, a, a, i);
+    slice(no, no, b, b, i + 1);
+  };
+
+  stage(0);
+  if (nfull >= 2) {
+    issue(wa[0], 0);
+    issue(wa[1], 1);
+    // whole turns of the three sets in the loop, so that each set is one
+    // fixed group of registers all the way round
+    const int nsteady = nfull - 2;  // slices with a slice i+2 to issue
+    int i = 0;
+    for (; i + 3 <= nsteady; i += 3) {
+      slice(yes, yes, wa[0], wa[2], i);
+      slice(yes, yes, wa[1], wa[0], i + 1);
+      slice(yes, yes, wa[2], wa[1], i + 2);
+    }
+    if (nsteady - i == 0) {
+      last2(wa[0], wa[1], i);
+    } else if (nsteady - i == 1) {
+      slice(yes, yes, wa[0], wa[2], i);
+      last2(wa[1], wa[2], i + 1);
+    } else {
+      slice(yes, yes, wa[0], wa[2], i);
+      slice(yes, yes, wa[1], wa[0], i + 1);
+      last2(wa[2], wa[0], i + 2);
+    }
+  } else if (nfull == 1) {
+    issue(wa[0], 0);
+    slice(no, no, wa[0], wa[0], 0);
+  }
+  if (has_tail) {
+    // klen == 128: one 128-k chunk at a time, nothing else in flight (its
+    // x was staged during the last whole slice, or above)
+    const long ks = ks0 + (long)nfull * kstride;
+    const int klen = (int)(K - ks);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    for (int kc0 = 0; kc0 < klen; kc0 += 128)
+      w4_consume<MT>(
+          nt_load16(wrow + (long)nfull * (kstride / 2) + kc0 / 2),
+          *reinterpret_cast<const unsigned int*>(
+              srow + (long)nfull * (kstride / 32) + kc0 / 32),
+          kgrp,
+          xbuf[nfull & 1], acc, kc0 + 32 * kgrp, row16);
+  }
+
+  // C layout: lane -> M index = lane&15, N index = n0 + 4*(lane>>4) + r
+  const int ncol = n0 + 4 * kgrp;
+  float* slab = SPLIT ? ws + (long)blockIdx.y * M * N : nullptr;
+#pragma unroll
+  for (int m = 0; m < MT; ++m) {
+    const int mrow = m * 16 + row16;
+    if (mrow >= M) continue;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const long off = (long)mrow * N + ncol + r;
+      if (SPLIT) {
+        slab[off] = acc[m][r];
+      } else {
+        out[off] = f2us(acc[m][r]);
+      }
+    }
+  }
+}
+
+// ===========================================================================
 // Host side. Every variant is the same algorithm: split K over ~256 blocks,
 // run the GEMM kernel straight to bf16 (splitk == 1) or into splitk f32
 // slabs, then one of two epilogues. A variant differs only in its plan
@@ -1222,6 +1432,9 @@ static SkinnyPlan plan_v6(int M, int N, long K, int KS) {
 static SkinnyPlan plan_w8(int M, int N, long K) {
   return skinny_plan(M, N, K, 64, KSLICE, 512, "KUKEON_W8_SPLITK");
 }
+static SkinnyPlan plan_w4(int M, int N, long K) {
+  return skinny_plan(M, N, K, 64, KSLICE, 512, "KUKEON_W4_SPLITK");
+}
 
 // The split-K factor a launcher will use, for sizing its workspace
 // (64 * N * splitk floats cover every M). Host-only.
@@ -1235,6 +1448,7 @@ int64_t skinny_splitk(const std::string& kind, int64_t N, int64_t K) {
   if (kind == "v6")
     return plan_v6(1, n, K, ks_from_env("KUKEON_SK6_KS")).splitk;
   if (kind == "w8") return plan_w8(1, n, K).splitk;
+  if (kind == "w4") return plan_w4(1, n, K).splitk;
   TORCH_CHECK(false, "skinny_splitk: unknown kind ", kind);
 }
 
@@ -1516,6 +1730,68 @@ void skinny_gemm_w8_fused_norm(torch::Tensor normed, torch::Tensor x,
               nw.numel() == q.size(0));
   const SkinnyPlan p = plan_w8(x.size(0), q.size(0), x.size(1));
   run_reduce_add_rmsnorm(p, w8_gemm(p, x, q, scale), normed, ws, residual,
+                         nw, eps);
+}
+
+// ---- W4A16 entry points: MXFP4 codes + per-block e8m0 scales ----
+static void check_w4(const torch::Tensor& x, const torch::Tensor& q,
+                     const torch::Tensor& scale) {
+  TORCH_CHECK(x.dim() == 2 && q.dim() == 2 && scale.dim() == 2 &&
+              x.size(1) == 2 * q.size(1) &&
+              scale.size(0) == q.size(0) && x.size(1) == 32 * scale.size(1),
+              "skinny gemm w4: x [M, K], q [N, K/2], scale [N, K/32]");
+  TORCH_CHECK(q.size(0) % 64 == 0 && x.size(1) % 128 == 0,
+              "skinny gemm w4: N%64, K%128");
+  TORCH_CHECK(q.scalar_type() == torch::kUInt8 &&
+              scale.scalar_type() == torch::kUInt8 &&
+              x.scalar_type() == torch::kBFloat16);
+  TORCH_CHECK(scale.is_contiguous() && q.is_contiguous());
+  TORCH_CHECK((uintptr_t)q.data_ptr() % 16 == 0 &&
+              (uintptr_t)scale.data_ptr() % 4 == 0,
+              "skinny gemm w4: q 16-byte and scale 4-byte aligned");
+  TORCH_CHECK(x.is_cuda() && q.is_cuda() && scale.is_cuda());
+}
+
+static auto w4_gemm(const SkinnyPlan& p, const torch::Tensor& x,
+                    const torch::Tensor& q, const torch::Tensor& scale) {
+  return [=, &p](bool is_split, unsigned short* out, float* ws, dim3 grid,
+                 hipStream_t stream) {
+    const unsigned char* qp = q.data_ptr<unsigned char>();
+    const unsigned char* sp = scale.data_ptr<unsigned char>();
+    with_mt(p.MT, [&](auto mt) {
+      constexpr int MT = decltype(mt)::value;
+      if (is_split) {
+        skinny_w4_kernel<MT, true><<<grid, 256, 0, stream>>>(
+            out, ws, us_ptr(x), qp, sp, p.M, p.N, p.K);
+      } else {
+        skinny_w4_kernel<MT, false><<<grid, 256, 0, stream>>>(
+            out, ws, us_ptr(x), qp, sp, p.M, p.N, p.K);
+      }
+    });
+  };
+}
+
+void skinny_gemm_w4(torch::Tensor out, torch::Tensor x, torch::Tensor q,
+                    torch::Tensor scale, torch::Tensor ws) {
+  check_w4(x, q, scale);
+  check_plain(out, x, q, 64, 128);
+  TORCH_CHECK(out.scalar_type() == torch::kBFloat16 &&
+              out.numel() == x.size(0) * q.size(0));
+  const SkinnyPlan p = plan_w4(x.size(0), q.size(0), x.size(1));
+  run_reduce(p, w4_gemm(p, x, q, scale), out, ws);
+}
+
+void skinny_gemm_w4_fused_norm(torch::Tensor normed, torch::Tensor x,
+                               torch::Tensor q, torch::Tensor scale,
+                               torch::Tensor ws, torch::Tensor residual,
+                               torch::Tensor nw, double eps) {
+  check_w4(x, q, scale);
+  check_fused(normed, x, q, residual, x.size(1), 128);
+  TORCH_CHECK(normed.numel() == x.size(0) * q.size(0) &&
+              residual.numel() == normed.numel() &&
+              nw.numel() == q.size(0));
+  const SkinnyPlan p = plan_w4(x.size(0), q.size(0), x.size(1));
+  run_reduce_add_rmsnorm(p, w4_gemm(p, x, q, scale), normed, ws, residual,
                          nw, eps);
 }
 

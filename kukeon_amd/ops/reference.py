@@ -353,6 +353,70 @@ def linear_w8(x: torch.Tensor, q: torch.Tensor,
     return (x.float() @ wf.T).to(x.dtype)
 
 
+# ---- MXFP4 (OCP MX: e2m1 codes, one e8m0 scale per 32 along K) ----
+# magnitude of e2m1 code & 7
+E2M1_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+MX_BLOCK = 32
+
+
+def quantize_mxfp4_rows(q: torch.Tensor, scale: torch.Tensor,
+                        w: torch.Tensor) -> None:
+    """The project's MXFP4 quantisation rule, which the GPU kernel matches
+    bit for bit. w bf16 [N, K], K % 32 == 0; q uint8 [N, K/2] (element 2j
+    in the low nibble, 2j+1 in the high one), scale uint8 [N, K/32].
+
+    Per block of 32: the scale byte is floor(log2 amax) - 2 + 127 clamped
+    to [1, 254] (127 for an all-zero block), so the block's largest element
+    lands on 4 or 6. floor(log2) is read off amax's exponent field: bf16
+    and f32 share it, and a subnormal amax clamps to 1 either way. With
+    X = 2^(byte - 127), |w| / X is exact in f32 and rounds to the nearest
+    of the eight magnitudes, ties to the even code, above 6 to 6."""
+    N, K = w.shape
+    assert K % MX_BLOCK == 0
+    wf = w.float().view(N, K // MX_BLOCK, MX_BLOCK)
+    amax = wf.abs().amax(dim=2)
+    ebits = (amax.contiguous().view(torch.int32) >> 23) & 0xFF
+    byte = torch.where(amax > 0, (ebits - 2).clamp(1, 254),
+                       torch.full_like(ebits, 127))
+    scale.copy_(byte.to(torch.uint8))
+    X = torch.pow(2.0, (byte - 127).double()).float()
+    v = wf.abs() / X[:, :, None]
+    # midpoints of the grid; a tie goes to the even code (the one whose
+    # mantissa bit is clear), hence > at the odd-below and >= at the
+    # even-above midpoints
+    code = ((v > 0.25).int() + (v >= 0.75).int() + (v > 1.25).int()
+            + (v >= 1.75).int() + (v > 2.5).int() + (v >= 3.5).int()
+            + (v > 5.0).int())
+    sign = (w.view(torch.int16).int() >> 12) & 8
+    code = (code.view(N, K) | sign).to(torch.uint8)
+    q.copy_(code[:, 0::2] | (code[:, 1::2] << 4))
+
+
+def _mxfp4_values(q: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """The exact f32 weight [N, K] an MXFP4 (q, scale) pair stands for."""
+    N, K = q.shape[0], q.shape[1] * 2
+    code = torch.stack([q & 0xF, q >> 4], dim=2).view(N, K).long()
+    mag = torch.tensor(E2M1_VALUES, dtype=torch.float32,
+                       device=q.device)[code & 7]
+    val = torch.where((code & 8) != 0, -mag, mag)
+    X = torch.pow(2.0, (scale.int() - 127).double()).float()
+    return (val.view(N, K // MX_BLOCK, MX_BLOCK) * X[:, :, None]).view(N, K)
+
+
+def dequant_mxfp4_rows(out: torch.Tensor, q: torch.Tensor,
+                       scale: torch.Tensor) -> None:
+    """out[n, k] = value(code[n, k]) * 2^(scale[n, k // 32] - 127): exact
+    in bf16 while the result is a normal number."""
+    out.copy_(_mxfp4_values(q, scale).to(out.dtype))
+
+
+def linear_w4(x: torch.Tensor, q: torch.Tensor,
+              scale: torch.Tensor) -> torch.Tensor:
+    """x @ deq(q, scale)^T in f32 on the exact dequantised weight, rounded
+    once to x's dtype."""
+    return (x.float() @ _mxfp4_values(q, scale).T).to(x.dtype)
+
+
 def decode_advance(ids, pos, seq_lens, tokens, ring, counter) -> None:
     step = int(counter[0])
     B = ids.shape[0]

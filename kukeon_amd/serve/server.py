@@ -55,6 +55,10 @@ class _Pending:
 
 
 class ModelhubServer:
+    # how long stop() waits for the engine loop to leave (under EP: for
+    # the other ranks to finish their work and vote stop as well)
+    STOP_JOIN_SECONDS = 300.0
+
     def __init__(self, model, cfg, ecfg: EngineConfig, socket_path: str,
                  device: str = "cuda:0"):
         self.engine = LLMEngine(model, cfg, ecfg, device=device)
@@ -66,6 +70,7 @@ class ModelhubServer:
         self._stop = threading.Event()
         self._srv = None
         self._threads = []
+        self._engine_thread = None
         self.metrics = {"tokens_generated": 0, "turns_completed": 0,
                         "engine_steps": 0, "busy_seconds": 0.0}
         # last-N turn latencies (seconds) for the stats percentiles —
@@ -395,6 +400,7 @@ class ModelhubServer:
         te = threading.Thread(target=self._engine_loop, daemon=True)
         te.start()
         self._threads.append(te)
+        self._engine_thread = te
         log.info("modelhub serving on %s", sp)
 
     def stop(self):
@@ -403,6 +409,18 @@ class ModelhubServer:
         if self._srv:
             self._srv.shutdown()
             self._srv.server_close()
+        # Return only once the engine loop has left. Under EP it keeps
+        # running collectives (participation passes for the other ranks)
+        # until every rank has voted stop: a caller that tore the process
+        # group down right after stop() did so under a collective in
+        # flight, which aborted this process or hung the rank still
+        # serving, whichever way the timing fell.
+        te = self._engine_thread
+        if te is not None and te is not threading.current_thread():
+            te.join(timeout=self.STOP_JOIN_SECONDS)
+            if te.is_alive():
+                log.warning("engine loop still running %.0f s after stop()",
+                            self.STOP_JOIN_SECONDS)
 
 
 class ModelhubClient:
@@ -479,9 +497,12 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--max-sessions", type=int, default=256)
     ap.add_argument("--no-graphs", action="store_true")
     ap.add_argument("--kv-blocks", type=int, default=0)
-    ap.add_argument("--weight-dtype", choices=("bf16", "fp8"), default=None,
+    ap.add_argument("--weight-dtype", choices=("bf16", "fp8", "mxfp4"),
+                    default=None,
                     help="GEMM weight storage; fp8 = e4m3 weight-only "
-                         "quantisation with per-output-channel scales "
+                         "quantisation with per-output-channel scales, "
+                         "mxfp4 = OCP MXFP4 (e2m1 codes, one e8m0 scale per "
+                         "32 along K; Llama only) "
                          "(default: KUKEON_WEIGHT_DTYPE, else bf16)")
     ap.add_argument("--shared-prefix-min-tokens", type=int, default=None,
                     help="decode attention reads the KV prefix that forked "
