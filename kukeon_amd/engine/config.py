@@ -106,6 +106,14 @@ class EngineConfig:
     # tokens (ops.paged_attention_shared); 0 = never. docs/perf.md has the
     # measurement behind the default.
     shared_prefix_min_tokens: int = SHARED_PREFIX_MIN_TOKENS_DEFAULT
+    # host KV tier: an idle session evicted under pressure keeps its KV in
+    # this many blocks of (pinned) host memory and its next turn copies it
+    # back; 0 = no host tier, eviction drops the KV and the next turn
+    # re-prefills the history
+    kv_host_blocks: int = 0
+    # device staging records a swap moves per chunk (one block each, K and
+    # V of all layers: 2 MiB on Llama-3-8B bf16)
+    kv_swap_staging_blocks: int = 64
 
     @property
     def max_blocks_per_seq(self) -> int:

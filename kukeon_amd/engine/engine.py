@@ -16,7 +16,8 @@ inference plane at all):
 * split-KV decode attention (matrix-core kernel, 4 autonomous wave-slots
   per workgroup) is split to ~4096 wave-units so the chip stays full even
   at small batch; idle sessions' KV evicts under pressure (history
-  recompute) and running rows preempt-by-recompute on exhaustion.
+  recompute, or a swap to pinned host memory when kv_host_blocks > 0) and
+  running rows preempt-by-recompute on exhaustion.
 """
 from __future__ import annotations
 
@@ -29,7 +30,7 @@ import torch
 
 from kukeon_amd import ops
 from kukeon_amd.engine.config import EngineConfig, ModelConfig, SamplingParams
-from kukeon_amd.engine.kv_cache import PagedKVCache, SequenceKV
+from kukeon_amd.engine.kv_cache import HostKVPool, PagedKVCache, SequenceKV
 from kukeon_amd.models.llama import AttnMeta
 
 log = logging.getLogger("kukeon.engine")
@@ -95,6 +96,24 @@ class LLMEngine:
                                dtype=kv_torch_dtype)
         log.info("KV cache: %d blocks (%.1f GiB for K+V)", nblocks,
                  self.kv.k.nbytes * 2 / (1 << 30))
+        # host KV tier (off by default): where _evict_idle_kv puts an idle
+        # session's exclusive blocks instead of dropping them
+        self.host_kv: Optional[HostKVPool] = None
+        if ecfg.kv_host_blocks > 0:
+            self.host_kv = HostKVPool(self.kv, ecfg.kv_host_blocks,
+                                      ecfg.kv_swap_staging_blocks)
+            log.info("host KV tier: %d blocks (%.1f GiB%s), %d staging",
+                     ecfg.kv_host_blocks,
+                     self.host_kv.pool.nbytes / (1 << 30),
+                     ", pinned" if self.is_cuda else "",
+                     self.host_kv.staging_blocks)
+        self.swap_out_blocks = 0    # blocks copied to the host tier, ever
+        self.swap_in_blocks = 0     # blocks copied back
+        self.swap_fallbacks = 0     # evictions that dropped, tier being on
+        # sessions that hold host blocks right now: a plain int kept where
+        # host_blocks turns non-empty or empty, so other threads (the
+        # server's stats) can read it
+        self.swapped_sessions = 0
 
         self.waiting: List[Request] = []
         self._next_id = 0
@@ -207,8 +226,37 @@ class LLMEngine:
                                     ctx_start=kv.num_tokens))
         return rid
 
+    def _host_tier(self) -> HostKVPool:
+        """The pool that a session's host blocks live in."""
+        if self.host_kv is None:
+            raise RuntimeError("a session holds host KV blocks but the "
+                               "engine has no host tier")
+        return self.host_kv
+
+    def _free_host_blocks(self, kv: SequenceKV) -> None:
+        if kv.host_blocks:
+            self._host_tier().allocator.free(kv.host_blocks)
+            kv.host_blocks = []
+            self.swapped_sessions -= 1
+
+    def _swap_in(self, kv: SequenceKV,
+                 blocks: Optional[List[int]] = None) -> None:
+        """Bring kv's host blocks back into device blocks (`blocks`, or
+        newly allocated ones), behind the ones that stayed."""
+        n = len(kv.host_blocks)
+        assert n > 0
+        tier = self._host_tier()
+        if blocks is None:
+            blocks = self.kv.allocator.alloc(n)
+        tier.load(kv.host_blocks, blocks)
+        kv.blocks.extend(blocks)
+        kv.host_blocks = []
+        self.swapped_sessions -= 1
+        self.swap_in_blocks += n
+
     def free_sequence(self, kv: SequenceKV) -> None:
         self.kv.allocator.free(kv.blocks)
+        self._free_host_blocks(kv)
         kv.blocks = []
         kv.num_tokens = 0
         kv.pending_token = None
@@ -222,7 +270,9 @@ class LLMEngine:
         `src` must have no active request — its tail is being written
         otherwise. MemoryError (pool cannot supply the tail blocks) leaves
         every reference count as it was. An evicted source forks to
-        children that carry only its history and re-prefill like it.
+        children that carry only its history and re-prefill like it; one
+        swapped out to the host tier is swapped in first, and a MemoryError
+        leaves it swapped out.
 
         Sharing is safe without copy-on-write because shared blocks are
         immutable: only blocks wholly below num_tokens are shared, that
@@ -239,8 +289,15 @@ class LLMEngine:
         bs = self.ecfg.block_size
         full, tail = divmod(src.num_tokens, bs)
         alloc = self.kv.allocator
-        # first, and the only step that can fail: nothing to undo
-        tails = alloc.alloc(n) if tail else []
+        # first, and the only step that can fail: nothing to undo. A source
+        # swapped out to the host tier comes back first, its blocks taken in
+        # the same all-or-nothing allocation as the tails.
+        back = len(src.host_blocks)
+        want = back + (n if tail else 0)
+        got = alloc.alloc(want) if want else []
+        tails = got[back:]
+        if back:
+            self._swap_in(src, got[:back])
         shared = src.blocks[:full]
         children = []
         for i in range(n):
@@ -319,7 +376,11 @@ class LLMEngine:
         request) to unblock admission; its history stays so the next
         request on that session transparently re-prefills the context.
         Sessions idle in HBM are the norm for agent serving — without
-        this, resident-but-idle context starves new admissions forever."""
+        this, resident-but-idle context starves new admissions forever.
+        With a host tier (kv_host_blocks > 0) the victim's exclusive blocks
+        are swapped out instead (_swap_out) and its next turn copies them
+        back; it is dropped as above only when that cannot be done. Every
+        call that returns True shortens some session's block list."""
         active = {id(r.kv) for r in self.waiting}
         active.update(id(r.kv) for r in self._rows if r is not None)
         # rank by what the eviction returns to the pool: blocks shared with
@@ -335,11 +396,50 @@ class LLMEngine:
                 victim, gain = kv, g
         if victim is None:
             return False
+        if self.host_kv is not None and self._swap_out(victim):
+            return True
         log.info("evicting idle session KV (%d blocks, %d to the pool) to "
                  "unblock admission", len(victim.blocks), gain)
+        self.swap_fallbacks += self.host_kv is not None
         self.kv.allocator.free(victim.blocks)
+        self._free_host_blocks(victim)
         victim.blocks = []
         victim.num_tokens = 0
+        return True
+
+    def _swap_out(self, kv: SequenceKV) -> bool:
+        """Move an idle session's exclusive blocks to the host tier instead
+        of dropping them: num_tokens and history stay, kv.blocks keeps what
+        stayed on the device and kv.host_blocks names the rest, in position
+        order. Blocks shared with a fork are a prefix of the list (forks
+        share src.blocks[:full]) and stay where they are with their
+        references, so sharing and shared-prefix decode survive; what moves
+        is the longest suffix of the blocks covering num_tokens that only
+        this session holds. Blocks reserved beyond num_tokens are freed.
+        -> False, with nothing changed, when that suffix is empty or the
+        host pool cannot take it. The device blocks go back to the free
+        list as soon as the copies are enqueued: whatever writes them next
+        is enqueued behind those on the same stream."""
+        alloc = self.kv.allocator
+        bs = self.ecfg.block_size
+        # device blocks that cover context; a session swapped out before
+        # (its shared prefix has since become its own) has the rest on the
+        # host already
+        cover = (kv.num_tokens + bs - 1) // bs - len(kv.host_blocks)
+        first = cover
+        while first > 0 and alloc.num_exclusive(kv.blocks[first - 1:first]):
+            first -= 1
+        moving = kv.blocks[first:cover]
+        if not moving or len(moving) > self.host_kv.allocator.num_free:
+            return False
+        log.info("swapping idle session KV to the host (%d of %d blocks) to "
+                 "unblock admission", len(moving), len(kv.blocks))
+        stored = self.host_kv.store(moving)
+        self.swapped_sessions += not kv.host_blocks
+        kv.host_blocks = stored + kv.host_blocks
+        alloc.free(kv.blocks[first:])
+        del kv.blocks[first:]
+        self.swap_out_blocks += len(moving)
         return True
 
     # ------------------------------------------------------------------
@@ -407,6 +507,11 @@ class LLMEngine:
         for s, (req, chunk) in enumerate(batch):
             toks = req.prompt_tokens[req.prefill_pos:
                                      req.prefill_pos + chunk]
+            if req.kv.host_blocks:
+                # swapped out while idle: admission counted these blocks
+                # (blocks_needed sees only kv.blocks), so this cannot fail;
+                # the turn then continues at num_tokens like a resident one
+                self._swap_in(req.kv)
             start = req.kv.num_tokens
             sl = self._alloc_for(req, chunk)
             req.kv.history.extend(toks)
@@ -641,6 +746,8 @@ class LLMEngine:
         recompute (history + its un-processed last token become the new
         prompt; already-emitted output_tokens are preserved)."""
         log.warning("preempting request %d (KV exhausted)", req.req_id)
+        # only idle sessions are swapped out, and a turn swaps in first
+        assert not req.kv.host_blocks
         self._release_row(req)
         history = list(req.kv.history)
         last = req.output_tokens[-1] if req.output_tokens else None

@@ -13,6 +13,8 @@ from typing import List
 
 import torch
 
+from kukeon_amd import ops
+
 
 class BlockAllocator:
     """Free-list block allocator with a reference count per block.
@@ -89,6 +91,10 @@ class SequenceKV:
         # every token whose K/V lives in the cache, in order — the replay
         # source for preemption-by-recompute
         self.history = []
+        # host-tier blocks (HostKVPool ids) of a session swapped out while
+        # idle: the positions after those `blocks` still covers, in order.
+        # blocks_needed() then counts the device blocks a swap-in takes.
+        self.host_blocks: List[int] = []
 
     def blocks_needed(self, new_tokens: int) -> int:
         total = self.num_tokens + new_tokens
@@ -127,3 +133,88 @@ class PagedKVCache:
                           dtype_bytes: int = 2) -> int:
         per_block = 2 * num_layers * num_kv_heads * block_size * head_dim * dtype_bytes
         return max(1, free_bytes // per_block)
+
+
+class HostKVPool:
+    """A second KV tier in host memory for sessions that idle: whole blocks
+    leave the paged caches for it and come back bit for bit.
+
+    `pool` is [host_blocks, record_bytes] uint8, pinned when the cache is on
+    a GPU; a record is one block's K then V for all layers, the layout of
+    the device staging buffer [staging_blocks, 2, L, Hk, BS, D]
+    (ops.kv_pack_blocks). A store packs up to staging_blocks blocks into the
+    staging buffer and copies each run of consecutive host ids with one
+    copy_(non_blocking=True); a load is the reverse. Everything is enqueued
+    on the current stream, in order. That ordering is what lets the caller
+    hand the device blocks back to its allocator as soon as store returns,
+    lets the staging buffer be reused chunk after chunk, and lets a host
+    block be reused right after load returns. There is no copy stream and
+    no overlap with compute."""
+
+    def __init__(self, cache: PagedKVCache, host_blocks: int,
+                 staging_blocks: int):
+        L, _, Hk, BS, D = cache.k.shape
+        dev = cache.k.device
+        self.cache = cache
+        self.num_blocks = host_blocks
+        self.staging_blocks = max(1, staging_blocks)
+        self.record_bytes = self.record_bytes_for(L, Hk, BS, D,
+                                                  cache.k.element_size())
+        self.pool = torch.empty(host_blocks, self.record_bytes,
+                                dtype=torch.uint8,
+                                pin_memory=dev.type == "cuda")
+        self.allocator = BlockAllocator(host_blocks)
+        self._staging_bytes = torch.zeros(self.staging_blocks,
+                                          self.record_bytes,
+                                          dtype=torch.uint8, device=dev)
+        self.staging = self._staging_bytes.view(cache.k.dtype).view(
+            self.staging_blocks, 2, L, Hk, BS, D)
+
+    @staticmethod
+    def record_bytes_for(num_layers: int, num_kv_heads: int, block_size: int,
+                         head_dim: int, dtype_bytes: int = 2) -> int:
+        return 2 * num_layers * num_kv_heads * block_size * head_dim * \
+            dtype_bytes
+
+    @staticmethod
+    def _runs(ids: List[int]):
+        """-> (offset, first id, length) of each run of consecutive ids."""
+        i = 0
+        while i < len(ids):
+            j = i + 1
+            while j < len(ids) and ids[j] == ids[j - 1] + 1:
+                j += 1
+            yield i, ids[i], j - i
+            i = j
+
+    def store(self, blocks: List[int]) -> List[int]:
+        """Copy the device blocks to newly allocated host blocks, returned
+        in the same order. MemoryError (pool cannot take them all) happens
+        before anything is enqueued or allocated."""
+        host = self.allocator.alloc(len(blocks))
+        cap = self.staging_blocks
+        dev = self.cache.k.device
+        for c in range(0, len(blocks), cap):
+            ids = torch.tensor(blocks[c:c + cap], dtype=torch.int32,
+                               device=dev)
+            ops.kv_pack_blocks(self.cache.k, self.cache.v, ids, self.staging)
+            for off, h0, m in self._runs(host[c:c + cap]):
+                self.pool[h0:h0 + m].copy_(self._staging_bytes[off:off + m],
+                                           non_blocking=True)
+        return host
+
+    def load(self, host: List[int], blocks: List[int]) -> None:
+        """Copy the host blocks into the (distinct, caller-owned) device
+        blocks and free the host blocks."""
+        assert len(host) == len(blocks)
+        cap = self.staging_blocks
+        dev = self.cache.k.device
+        for c in range(0, len(host), cap):
+            for off, h0, m in self._runs(host[c:c + cap]):
+                self._staging_bytes[off:off + m].copy_(self.pool[h0:h0 + m],
+                                                       non_blocking=True)
+            ids = torch.tensor(blocks[c:c + cap], dtype=torch.int32,
+                               device=dev)
+            ops.kv_unpack_blocks(self.staging, self.cache.k, self.cache.v,
+                                 ids)
+        self.allocator.free(host)

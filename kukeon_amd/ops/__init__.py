@@ -83,6 +83,26 @@ def kv_copy_blocks(k_cache, v_cache, src, dst) -> None:
     _impl(k_cache).kv_copy_blocks(k_cache, v_cache, src, dst)
 
 
+def kv_pack_blocks(k_cache, v_cache, blocks, staging) -> None:
+    """staging[i, s, l] = cache_s[l, blocks[i]] for every layer l, both
+    sides s (0 = K, 1 = V) and every listed block i, as raw bytes (bf16 and
+    fp8 caches alike) in one launch; an empty list launches nothing. The
+    caches are [L, NB, Hk, BS, D]; `staging` is [cap, 2, L, Hk, BS, D] of the
+    caches' dtype, so record i is one block of all layers, contiguous — the
+    unit a copy to host memory moves. `blocks` is a contiguous int32 tensor
+    of at most cap ids on the caches' device; records from len(blocks) on
+    are left untouched."""
+    _impl(k_cache).kv_pack_blocks(k_cache, v_cache, blocks, staging)
+
+
+def kv_unpack_blocks(staging, k_cache, v_cache, blocks) -> None:
+    """cache_s[l, blocks[i]] = staging[i, s, l]: the inverse of
+    kv_pack_blocks, with the same shapes and checks. The destination blocks
+    must be distinct, which the caller guarantees; no other block is
+    written."""
+    _impl(k_cache).kv_unpack_blocks(staging, k_cache, v_cache, blocks)
+
+
 def decode_advance(ids, pos, seq_lens, tokens, ring, counter) -> None:
     _impl(ids).decode_advance(ids, pos, seq_lens, tokens, ring, counter)
 

@@ -23,6 +23,7 @@ SOURCES = [
     "activation.hip",
     "rope_kv.hip",
     "kv_copy.hip",
+    "kv_swap.hip",
     "paged_attn.hip",
     "prefill_attn.hip",
     "mfma_probe.hip",

@@ -17,6 +17,10 @@ void decode_advance(torch::Tensor ids, torch::Tensor pos,
                     torch::Tensor ring, torch::Tensor counter);
 void kv_copy_blocks(torch::Tensor k_cache, torch::Tensor v_cache,
                     torch::Tensor src, torch::Tensor dst);
+void kv_pack_blocks(torch::Tensor k_cache, torch::Tensor v_cache,
+                    torch::Tensor blocks, torch::Tensor staging);
+void kv_unpack_blocks(torch::Tensor staging, torch::Tensor k_cache,
+                      torch::Tensor v_cache, torch::Tensor blocks);
 void paged_attention(torch::Tensor out, torch::Tensor q, torch::Tensor k_cache,
                      torch::Tensor v_cache, torch::Tensor block_table,
                      torch::Tensor seq_lens, int64_t q_offset,
@@ -122,6 +126,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("kv_copy_blocks", &kukeon::kv_copy_blocks,
         "cache[l, dst[i]] = cache[l, src[i]] for K and V, all layers, one "
         "launch");
+  m.def("kv_pack_blocks", &kukeon::kv_pack_blocks,
+        "staging[i, s, l] = cache_s[l, blocks[i]] for K and V, all layers, "
+        "one launch");
+  m.def("kv_unpack_blocks", &kukeon::kv_unpack_blocks,
+        "cache_s[l, blocks[i]] = staging[i, s, l] for K and V, all layers, "
+        "one launch");
   m.def("paged_attention", &kukeon::paged_attention,
         "decode paged attention (GQA, split-KV)");
   m.def("paged_attention_rope", &kukeon::paged_attention_rope,

@@ -98,6 +98,40 @@ def kv_copy_blocks(k_cache: torch.Tensor, v_cache: torch.Tensor,
     v_cache[:, dst.long()] = v_cache[:, src.long()]
 
 
+def _check_swap_args(k_cache, v_cache, blocks, staging) -> None:
+    assert k_cache.shape == v_cache.shape and k_cache.dtype == v_cache.dtype
+    L, _, Hk, BS, D = k_cache.shape
+    assert staging.dim() == 6 and tuple(staging.shape[1:]) == \
+        (2, L, Hk, BS, D) and staging.dtype == k_cache.dtype
+    assert blocks.dim() == 1 and blocks.numel() <= staging.shape[0]
+
+
+def kv_pack_blocks(k_cache: torch.Tensor, v_cache: torch.Tensor,
+                   blocks: torch.Tensor, staging: torch.Tensor) -> None:
+    """staging[i, s, l] = cache_s[l, blocks[i]] on [L, NB, Hk, BS, D] caches
+    and a [cap, 2, L, Hk, BS, D] staging buffer."""
+    _check_swap_args(k_cache, v_cache, blocks, staging)
+    n = blocks.numel()
+    if n == 0:
+        return
+    idx = blocks.long()
+    staging[:n, 0] = k_cache[:, idx].transpose(0, 1)
+    staging[:n, 1] = v_cache[:, idx].transpose(0, 1)
+
+
+def kv_unpack_blocks(staging: torch.Tensor, k_cache: torch.Tensor,
+                     v_cache: torch.Tensor, blocks: torch.Tensor) -> None:
+    """cache_s[l, blocks[i]] = staging[i, s, l]; the inverse of
+    kv_pack_blocks for distinct blocks."""
+    _check_swap_args(k_cache, v_cache, blocks, staging)
+    n = blocks.numel()
+    if n == 0:
+        return
+    idx = blocks.long()
+    k_cache[:, idx] = staging[:n, 0].transpose(0, 1)
+    v_cache[:, idx] = staging[:n, 1].transpose(0, 1)
+
+
 def _gather_kv(cache: torch.Tensor, block_table: torch.Tensor, ctx: int,
                b: int) -> torch.Tensor:
     """-> [ctx, Hk, D] from paged cache [NB, Hk, BS, D] (bf16 or fp8)."""

@@ -184,6 +184,7 @@ class ModelhubServer:
             return {"ok": True, "pid": os.getpid()}
         if method == "stats":
             kv = self.engine.kv
+            host = self.engine.host_kv
             lat = sorted(self._turn_latency)
 
             def pct(q: float) -> float:
@@ -199,6 +200,13 @@ class ModelhubServer:
                 "kv_blocks_total": kv.num_blocks,
                 "kv_blocks_free": kv.allocator.num_free,
                 "kv_blocks_shared": kv.allocator.num_shared,
+                "kv_host_blocks_total": host.num_blocks if host else 0,
+                "kv_host_blocks_free":
+                    host.allocator.num_free if host else 0,
+                "swap_out_blocks": self.engine.swap_out_blocks,
+                "swap_in_blocks": self.engine.swap_in_blocks,
+                "swapped_sessions": self.engine.swapped_sessions,
+                "swap_fallbacks": self.engine.swap_fallbacks,
                 "weight_dtype": getattr(self.engine.model, "weight_dtype",
                                         "bf16"),
                 "weight_bytes": _resident_weight_bytes(self.engine.model),
@@ -509,7 +517,27 @@ def build_parser() -> argparse.ArgumentParser:
                          "sessions share once per tile of sessions when it "
                          "has at least this many tokens; 0 = never "
                          "(default: EngineConfig's)")
+    ap.add_argument("--kv-host-gib", type=float, default=0.0,
+                    help="host memory (GiB, pinned on a GPU) for the KV of "
+                         "idle sessions evicted under pressure: their next "
+                         "turn copies it back instead of re-prefilling the "
+                         "history; 0 = no host tier")
+    ap.add_argument("--kv-swap-staging-blocks", type=int, default=None,
+                    help="KV blocks a swap moves per chunk through its "
+                         "device staging buffer (default: EngineConfig's)")
     return ap
+
+
+def kv_host_blocks_for(gib: float, cfg, ecfg: EngineConfig) -> int:
+    """Host blocks that fit `gib` GiB: a host block is one KV block's K and
+    V for all layers of this rank, in the cache's dtype."""
+    import kukeon_amd.parallel as parallel
+    from kukeon_amd.engine.kv_cache import HostKVPool
+    record = HostKVPool.record_bytes_for(
+        cfg.num_layers, cfg.num_kv_heads // max(1, parallel.tp_size()),
+        ecfg.block_size, cfg.head_dim,
+        dtype_bytes=1 if ecfg.kv_dtype == "fp8" else 2)
+    return int(gib * (1 << 30)) // record
 
 
 def main(argv: Optional[List[str]] = None) -> None:
@@ -525,6 +553,10 @@ def main(argv: Optional[List[str]] = None) -> None:
         use_graphs=not args.no_graphs and device != "cpu" and not cfg.is_moe)
     if args.shared_prefix_min_tokens is not None:
         ecfg.shared_prefix_min_tokens = max(0, args.shared_prefix_min_tokens)
+    if args.kv_swap_staging_blocks is not None:
+        ecfg.kv_swap_staging_blocks = max(1, args.kv_swap_staging_blocks)
+    if args.kv_host_gib > 0:
+        ecfg.kv_host_blocks = kv_host_blocks_for(args.kv_host_gib, cfg, ecfg)
     if cfg.is_moe:
         from kukeon_amd.models.mixtral import MixtralModel
         model = MixtralModel(cfg, device=device,
